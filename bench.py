@@ -9,14 +9,28 @@ reference's fixed-iteration mode (testing/ harness: updateY2 only).
 A *step* is one updateY2 of every problem of the batch (one PQP iteration of
 the whole job).  `value` = problems x steps over all ranks / max-over-ranks
 wall time of exactly K steps (inputs already resident in HBM), in
-instance-iterations per second.
+instance-iterations per second; `ms_per_step` = that wall time / K.
 
-Extra keys:
+A plain run (no --full) sets up, warms up, times the K steps, writes the
+outputs if --dump-outputs is given, and prints the headline line: nothing
+else is measured.  --dump-outputs DIR writes what the timed path returned
+after its last step, the iterate Y of every problem (what Batch.result()
+hands a caller), as DIR/Y.npy (float32; rank r of an N > 1 job writes
+DIR/Y_rank<r>.npy).  The inputs depend on the arguments alone (--seed), and
+the timed steps start from the reference's Y = 1000, so two builds run with
+the same arguments can be compared output for output.  At most DUMP_BYTES
+are written: of a larger output, a fixed, seeded sample of the problems.
+
+Headline keys:
   roofline      the fused update kernel vs the 8 TB/s HBM peak, algorithmic
                 bytes ALG(N) = 4N^2 + 16N per problem-iteration,
-                duration from HIP events on the launch stream; `traffic` is
-                the PMC-measured HBM bytes per launch (profiles/pmc_traffic.json)
-  cpu_baseline  PQP_CPU.c's own updateY2 (oracle/_ref, compiled from the
+                duration from HIP events around the timed steps themselves;
+                `traffic` is the PMC-measured HBM bytes per launch
+                (profiles/pmc_traffic.json)
+
+Extra keys, with --full only (each a measurement of its own, after the
+headline):
+  cpu_baselinePQP_CPU.c's own updateY2 (oracle/_ref, compiled from the
                 reference) -- or the bit-exact restatement if that build is
                 absent -- single thread on this host, bounded sample
   bundled       the bundled example (configs[0]/[1]) on 1 GPU through the
@@ -36,7 +50,9 @@ Extra keys:
                 bundled example, testing/ test1 and test2): h and time per
                 solve, with the reference's own h (cpu_baseline) beside it
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+  summary       every leg's headline numbers, last key of the line
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
        N > 1 either way:
          python bench.py --gpus N      (this process spawns N ranks itself, one
                                         per GPU, before it touches HIP; it
@@ -147,7 +163,7 @@ def valu_roofline(key: str, marker: str, h_sum: int, dt: float, N: int, M: int) 
     return out
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
@@ -157,6 +173,11 @@ def parse():
     ap.add_argument("--chunk", type=int, default=10,
                     help="iterations (steps) per kernel launch; the iterate stays in LDS between them")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the iterate Y they produced to DIR/Y.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other leg (CPU baseline, batch_converge, rowshard, "
+                         "bundled, mpc_batch, horizon, single, setup, iters_to_tol; the Y* gather at N > 1)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU-baseline sample budget")
     ap.add_argument("--cpu-instances", type=int, default=16,
                     help="distinct problems the CPU baseline cycles through (>= 8, DRAM-resident)")
@@ -172,7 +193,36 @@ def parse():
                     help="seconds an optional leg (gather, rowshard, ...) may run before the line is printed without it")
     ap.add_argument("--dist-timeout", type=float, default=300.0,
                     help="process-group timeout (s); longer than --leg-timeout")
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (the number of timed steps)")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+DUMP_BYTES = 48 << 20  # --dump-outputs writes at most this much, over all ranks
+
+
+def dump_outputs(directory, Y, rank: int = 0, world: int = 1) -> Path:
+    """Write the timed path's result `Y` ([problems][n_dual], a torch tensor
+    on any device) as float32 to <directory>/Y.npy (Y_rank<r>.npy at
+    world > 1).  Each rank keeps to DUMP_BYTES / world: of a larger result
+    it writes a sample of the problems (rows), drawn without replacement by a
+    generator of fixed seed and kept in ascending order -- the same rows on
+    every run with the same arguments."""
+    import numpy as np
+    import torch
+
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    rows_max = max(1, DUMP_BYTES // max(1, world) // (4 * Y.shape[1]))
+    if Y.shape[0] > rows_max:
+        rows = np.sort(np.random.default_rng(20240607).choice(Y.shape[0], rows_max, replace=False))
+        Y = Y[torch.from_numpy(rows).to(Y.device)]
+    path = out / ("Y.npy" if world == 1 else f"Y_rank{rank}.npy")
+    np.save(path, np.ascontiguousarray(Y.detach().cpu().numpy(), dtype=np.float32))
+    return path
 
 
 def host_cpu() -> dict:
@@ -1106,6 +1156,16 @@ def main():
     # optional legs run, each under the Emitter's guard.
     result = headline(args, rank, world, N, B, K, W, C, elapsed, kern_ms, launches, finite, rehearse,
                       spread=spread) if rank == 0 else None
+    if args.dump_outputs:  # the iterate the K timed steps left, as Batch.result() returns it
+        dump_outputs(args.dump_outputs, Yh, rank, world)
+    if not args.full:
+        # a plain run ends here: the headline alone (every further leg is a
+        # measurement of its own, behind --full)
+        if result is not None:
+            print(json.dumps(result), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     em = Emitter(rank, result, args.leg_timeout, abort_on_failure=world > 1)
 
     if dist is not None:  # gather Y* to rank 0 over RCCL (reported separately, not in `value`)

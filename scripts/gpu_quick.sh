@@ -1,5 +1,6 @@
 # Focused GPU check: named tests first, then the whole GPU suite, then the
-# lean-relay timing and a 1-GPU bench line without the CPU baseline.
+# lean-relay timing and a 1-GPU bench line with every leg but the CPU baseline
+# (bench.py --full; written to $OUT, default bench_out/).
 set -o pipefail
 cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out
@@ -18,6 +19,8 @@ timeout -k 10 600 bash -c "$EXTRA" > gpurun_out/extra_$TAG.txt 2>&1 || { tail -3
 tail -40 gpurun_out/extra_$TAG.txt
 fi
 if [ -z "$SKIP_BENCH" ]; then
-timeout -k 10 400 python -u bench.py ${BENCH_ARGS:---steps 20 --warmup 5 --no-cpu-baseline} > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err || { tail -30 gpurun_out/bench_$TAG.err; exit 1; }
-cat gpurun_out/bench_$TAG.json
+OUT=${OUT:-bench_out}
+mkdir -p "$OUT"
+timeout -k 10 400 python -u bench.py ${BENCH_ARGS:---full --steps 20 --warmup 5 --no-cpu-baseline} > "$OUT"/bench_$TAG.json 2> "$OUT"/bench_$TAG.err || { tail -30 "$OUT"/bench_$TAG.err; exit 1; }
+cat "$OUT"/bench_$TAG.json
 fi
