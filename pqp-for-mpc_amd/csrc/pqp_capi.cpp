@@ -33,19 +33,24 @@ struct DevBuf {
     DevBuf() = default;
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
+    // moves swap the pointer and its size together (the moved-from buffer
+    // frees what this one held)
+    DevBuf(DevBuf&& o) noexcept { swap(o); }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        swap(o);
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    void swap(DevBuf& o) {
+        std::swap(p, o.p);
+        std::swap(bytes_, o.bytes_);
     }
     // (re)allocate; a buffer of the same size is kept (same address: no
     // hipMalloc/hipFree pair, and graphs captured over it stay valid)
     int alloc(size_t bytes) {
         if (bytes == 0) bytes = 16;
         if (p && bytes == bytes_) return PQP_OK;
-        if (p) {
-            (void)hipFree(p);
-            p = nullptr;
-            bytes_ = 0;
-        }
+        reset();
         hipError_t e = hipMalloc(&p, bytes);
         if (e != hipSuccess) {
             p = nullptr;
@@ -61,6 +66,82 @@ struct DevBuf {
         p = nullptr;
         bytes_ = 0;
     }
+};
+
+// One pinned host block, grow-only: a request no larger than the block keeps
+// it (and its address).  `dev` is its device address when it was mapped
+// (hipHostMallocMapped).
+struct PinnedBuf {
+    void* p = nullptr;
+    void* dev = nullptr;
+    size_t bytes_ = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf&) = delete;
+    PinnedBuf& operator=(const PinnedBuf&) = delete;
+    ~PinnedBuf() { reset(); }
+    int reserve(size_t bytes, unsigned flags = hipHostMallocDefault) {
+        if (p && bytes <= bytes_) return PQP_OK;
+        reset();
+        PQP_HIP(hipHostMalloc(&p, bytes, flags));
+        bytes_ = bytes;
+        if (flags & hipHostMallocMapped) PQP_HIP(hipHostGetDevicePointer(&dev, p, 0));
+        return PQP_OK;
+    }
+    template <class T>
+    T* as() const { return static_cast<T*>(p); }
+    float* f() const { return as<float>(); }
+    void reset() {
+        if (p) (void)hipHostFree(p);
+        p = dev = nullptr;
+        bytes_ = 0;
+    }
+};
+
+// One instantiated hipGraph.
+struct GraphExec {
+    hipGraphExec_t exec = nullptr;
+    GraphExec() = default;
+    GraphExec(const GraphExec&) = delete;
+    GraphExec& operator=(const GraphExec&) = delete;
+    GraphExec(GraphExec&& o) noexcept { std::swap(exec, o.exec); }
+    GraphExec& operator=(GraphExec&& o) noexcept {
+        std::swap(exec, o.exec);
+        return *this;
+    }
+    ~GraphExec() { reset(); }
+    void reset() {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        exec = nullptr;
+    }
+    // Replace the graph by what body() (-> hipError_t) enqueues on s.  A
+    // failing body is reported before a failing end of the capture.
+    template <class Body>
+    int capture(hipStream_t s, Body&& body) {
+        reset();
+        hipGraph_t g = nullptr;
+        PQP_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+        const hipError_t e = body();
+        const hipError_t e2 = hipStreamEndCapture(s, &g);
+        if (e != hipSuccess || e2 != hipSuccess) {
+            if (g) (void)hipGraphDestroy(g);
+            PQP_HIP(e != hipSuccess ? e : e2);
+        }
+        const hipError_t e3 = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(g);
+        PQP_HIP(e3);
+        return PQP_OK;
+    }
+};
+
+// The relay update's operand for a block of rows of one problem (a whole
+// problem, or one pqp_rowblock): the stored split matrices with lw row sides
+// per workgroup and {Fdp, Fdn}, or (lean) Qd packets with lw / 2 rows per
+// workgroup (k_lean_relay, half the bytes) and the {Fdn, Fdp, Theta, 0} words.
+struct RelayBlock {
+    DevBuf SP, fdpn;
+    DevBuf err;  // sticky relay hand-off error word
+    int lw = 64;
+    bool lean = false;
 };
 
 // Verify that the current device is a gfx950 (the only code object we ship).
@@ -265,63 +346,63 @@ struct SolveOut {
 // serialized by its own lock, calls on different handles run concurrently
 // (the reference's solver keeps no globals, PQP_CPU.c:694).
 struct pqp_problem {
+    // (Members are destroyed last to first: the pinned blocks, the work
+    // buffers, what was derived, the inputs.  The order blocks go back to the
+    // allocator in decides where the process's later allocations land.)
+
+    // the problem: row-major device copies of the nine inputs
     int N = 0, M = 0;
-    int dev = -1;                 // the device every call of this handle runs on
-    hipStream_t stream = nullptr; // the handle's stream (owned unless the caller passed one)
+    pqp::DevBuf Qd, Fd, Md, Qp, Qinv, Fp, Mp, Gp, Kp;
+    bool small = false;  // fits k_solve_small (everything staged in LDS)
+
+    // Everything built on first use from the problem's data.  The captured
+    // graphs hold these buffers' addresses: the stream is idle when it is dropped.
+    struct Derived {
+        pqp::DevBuf QdT;    // the one-workgroup solver's column-major Qd (ensure_single)
+        pqp::DevBuf theta;  // ensure_theta
+        struct Relay {  // fixed mode on the graph-replayed relay; the wide chain's update
+            pqp::RelayBlock block;          // rows 0 .. N-1
+            pqp::GraphExec chunk, rem;      // kFixedChunk updates; the remainder
+            bool chunk_ready = false;
+            long long graph_updates = -1;   // updates `rem` was captured with
+            long long graph_variant = -1;   // the settings both were captured with
+        } relay;
+        pqp::DevBuf Yb;  // the second iterate of the multi-workgroup paths
+        struct Persist {  // persistent fixed mode: split matrices (lw = 32), y granules, error word
+            pqp::DevBuf SP, fdpn, gran, err;
+        } persist;
+        struct Wide {  // converge mode over many workgroups (pqp_wide.hip)
+            pqp::DevBuf QinvT, GpT, tM, tq, tu, gu, flag, cap;
+            pqp::GraphExec first, g4, g8, full;  // chunks of kWideFirstChunk, 4, 8, kWideChunk iterations
+            long long key = -1;                   // the settings they were captured with
+        } wide;
+        struct Converge {  // converge mode as one persistent pipelined launch (pqp_converge.hip)
+            pqp::DevBuf A1, A2, A3, rings, words;
+        } conv;
+    } d;
+
+    // handle-lifetime state: survives new data going into the handle
+    int dev = -1;                  // the device every call of this handle runs on
+    hipStream_t stream = nullptr;  // the handle's stream (owned unless the caller passed one)
     bool own_stream = false;
     std::mutex mu;
-    bool small = false;  // fits k_solve_small (everything staged in LDS)
-    pqp::DevBuf Qd, Fd, Md, Qp, Qinv, Fp, Mp, Gp, Kp;  // row-major device copies
-    pqp::DevBuf QdT, theta;                          // large path only
-    pqp::DevBuf SP, fdpn, Yb;                        // large path, fixed mode (built on first use)
-    pqp::DevBuf rerr;                                // sticky relay hand-off error word (relay / graph paths)
-    pqp::DevBuf SPp, fdpnp, gran, perr;              // persistent fixed mode: split matrices (lw = 32), y granules, error word
-    int split_lw = 0;                                // lanes per workgroup SP was built with
-    bool split_lean = false;                         // SP holds Qd packets (k_lean_relay), not the split matrices
-    hipGraphExec_t graph = nullptr;                  // captured fixed-mode updates (the remainder)
-    long long graph_updates = -1;
-    hipGraphExec_t chunk_graph = nullptr;            // captured fixed-mode chunk of kFixedChunk updates
-    bool chunk_ready = false;
-    // converge mode over many workgroups (pqp_wide.hip), built on first use
-    pqp::DevBuf QinvT, GpT, tM, tq, tu, gu, wflag, wcap;
-    // converge mode as one persistent pipelined launch (pqp_converge.hip), built on first use
-    pqp::DevBuf CA1, CA2, CA3, crings, cwords;
-    hipGraphExec_t wgraph = nullptr;                 // captured chunk of converge iterations
-    hipGraphExec_t wgraph_first = nullptr;           // the short first chunk
-    hipGraphExec_t wgraph4 = nullptr, wgraph8 = nullptr;  // the chunks that escalate to kWideChunk
-    long long wgraph_key = -1;
-    long long graph_variant = -1;                    // the settings the fixed-mode graphs were captured with
     pqp::DevBuf Y, U, state;
-    pqp::SolveState* hst = nullptr;                  // pinned host mirror of `state`
-    float* hio = nullptr;                            // pinned staging of Y (N floats) then U (M floats)
-    size_t hio_floats = 0;
-    float* hin = nullptr;                            // pinned staging of small problems' inputs
-    size_t hin_floats = 0;
-    float* hout = nullptr;                           // pinned output of the one-launch tiny solves (kTinyOut* layout)
-    unsigned out_tag = 0;                            // the last tag a tiny launch was given (1 .. 2^31 - 1)
-    void* hout_dev = nullptr;                        // its device address
+    pqp::PinnedBuf hout;  // mapped output of the one-launch tiny solves (kTinyOut* layout)
+    pqp::PinnedBuf hin;   // staging of small problems' inputs
+    pqp::PinnedBuf hio;   // staging of Y (N floats) then U (M floats)
+    pqp::PinnedBuf hst;   // host mirror of `state`
+    unsigned out_tag = 0;  // the last tag a tiny launch was given (1 .. 2^31 - 1)
+
     ~pqp_problem() {
         if (own_stream && stream) (void)hipStreamDestroy(stream);
-        if (graph) (void)hipGraphExecDestroy(graph);
-        if (chunk_graph) (void)hipGraphExecDestroy(chunk_graph);
-        if (wgraph) (void)hipGraphExecDestroy(wgraph);
-        if (wgraph_first) (void)hipGraphExecDestroy(wgraph_first);
-        if (wgraph4) (void)hipGraphExecDestroy(wgraph4);
-        if (wgraph8) (void)hipGraphExecDestroy(wgraph8);
-        if (hst) (void)hipHostFree(hst);
-        if (hio) (void)hipHostFree(hio);
-        if (hin) (void)hipHostFree(hin);
-        if (hout) (void)hipHostFree(hout);
     }
 };
 
 // One row block of a large problem's stored split matrices (pqp_rowblock_*).
 struct pqp_rowblock {
-    int N = 0, row0 = 0, rows = 0, lw = 64;
+    int N = 0, row0 = 0, rows = 0;
     int dev = -1;  // the device it was made on (its calls run there)
-    bool lean = false;  // SP holds Qd packets (k_lean_relay), fdpn the {Fdn, Fdp, Theta, 0} words
-    pqp::DevBuf SP, fdpn;
-    pqp::DevBuf err;    // sticky relay hand-off error word (pqp_rowblock_check)
+    pqp::RelayBlock relay;
 };
 
 namespace pqp {
@@ -332,9 +413,27 @@ namespace {
 constexpr size_t kLdsBudget = 150 * 1024;
 inline bool batch_unfused() { return (g_tune.batch_opts & 1) != 0; }
 
-// Allocate the per-problem work buffers and, for the large path, the
-// column-major copy and theta.  The nine input buffers must already hold the
-// problem.
+// Iterates per launch of a resumable solve: about `budget` element updates
+// (one iterate is 3 N^2 + 2 N M + 2 M^2 + 1 of them), at least `floor`.  So a
+// long fixed-mode solve or an uncapped converge solve is a sequence of
+// launches that resume from the device state, not one kernel running for
+// minutes.
+long long updates_per_launch(int N, int M, long long budget, long long floor) {
+    const double per_update = 3.0 * N * N + 2.0 * N * M + 2.0 * M * M + 1.0;
+    return std::max(floor, (long long)((double)budget / per_update));
+}
+
+// Theta (computeTheta, PQP_CPU.c:503-519), built on first use: with the
+// handle for a large problem, by the first multi-workgroup solve of a small one.
+int ensure_theta(pqp_problem& P, hipStream_t s) {
+    if (P.d.theta.p) return PQP_OK;
+    PQP_TRY(P.d.theta.floats(P.N));
+    PQP_HIP(launch_theta_rows(P.Qd.f(), P.N, P.N, P.N, P.d.theta.f(), s));
+    return PQP_OK;
+}
+
+// Allocate the per-problem work buffers and, for the large path, theta.  The
+// nine input buffers must already hold the problem.
 int problem_finish(pqp_problem& P, hipStream_t s) {
     const int N = P.N, M = P.M;
     P.small = solve_small_lds_bytes(N, M) <= kLdsBudget;
@@ -344,155 +443,124 @@ int problem_finish(pqp_problem& P, hipStream_t s) {
     PQP_TRY(P.state.alloc(sizeof(SolveState) + 16));
     PQP_HIP(hipMemsetAsync(P.state.p, 0, sizeof(SolveState) + 16, s));
     PQP_HIP(hipMemsetAsync(P.U.p, 0, sizeof(float) * M, s));
-    if (!P.hst) PQP_HIP(hipHostMalloc((void**)&P.hst, sizeof(SolveState), hipHostMallocDefault));
-    if (P.hio_floats < (size_t)N + M) {
-        if (P.hio) (void)hipHostFree(P.hio);
-        P.hio = nullptr;
-        P.hio_floats = 0;
-        PQP_HIP(hipHostMalloc((void**)&P.hio, sizeof(float) * ((size_t)N + M), hipHostMallocDefault));
-        P.hio_floats = (size_t)N + M;
-    }
-    if (!P.small) {  // Theta for the large paths (computeTheta, PQP_CPU.c:503-519)
-        PQP_TRY(P.theta.floats(N));
-        PQP_HIP(launch_theta_rows(P.Qd.f(), N, N, N, P.theta.f(), s));
-    }
+    PQP_TRY(P.hst.reserve(sizeof(SolveState)));
+    PQP_TRY(P.hio.reserve(sizeof(float) * ((size_t)N + M)));
+    if (!P.small) PQP_TRY(ensure_theta(P, s));
     return PQP_OK;
 }
 
 // The one-workgroup solver's column-major copy of Qd, built on first use (the
 // multi-workgroup paths do not need it).
 int ensure_single(pqp_problem& P, hipStream_t s) {
-    if (P.QdT.p) return PQP_OK;
+    if (P.d.QdT.p) return PQP_OK;
     const int N = P.N, M = P.M, ldq = round4(N);
     if (solve_single_lds_bytes(ldq, round4(M)) > kLdsBudget)
         return set_error(PQP_ERR_ARG,
                          "N=%d, M=%d exceeds the one-workgroup solver's LDS budget (terminate() drop-in / resumed "
                          "solves); converge and fixed mode run over many workgroups", N, M);
-    PQP_TRY(P.QdT.floats((size_t)N * ldq));
-    PQP_HIP(launch_pack_colmajor(1, P.Qd.f(), N, (long long)N * N, P.QdT.f(), ldq, (long long)N * ldq, s));
+    PQP_TRY(P.d.QdT.floats((size_t)N * ldq));
+    PQP_HIP(launch_pack_colmajor(1, P.Qd.f(), N, (long long)N * N, P.d.QdT.f(), ldq, (long long)N * ldq, s));
     return PQP_OK;
 }
 
 // Drop everything derived from a problem's data (built on first use by the
 // solve paths): called before new data goes into an existing handle.
-void problem_reset_derived(pqp_problem& P) {
-    for (DevBuf* b : {&P.QdT, &P.theta, &P.SP, &P.fdpn, &P.Yb, &P.rerr, &P.SPp, &P.fdpnp, &P.gran, &P.perr, &P.QinvT, &P.GpT,
-                      &P.tM, &P.tq, &P.tu, &P.gu, &P.wflag, &P.wcap, &P.CA1, &P.CA2, &P.CA3, &P.crings, &P.cwords})
-        b->reset();
-    for (hipGraphExec_t* g : {&P.graph, &P.chunk_graph, &P.wgraph, &P.wgraph_first, &P.wgraph4, &P.wgraph8})
-        if (*g) {
-            (void)hipGraphExecDestroy(*g);
-            *g = nullptr;
-        }
-    P.split_lw = 0;
-    P.split_lean = false;
-    P.graph_updates = -1;
-    P.chunk_ready = false;
-    P.graph_variant = -1;
-    P.wgraph_key = -1;
-}
+void problem_reset_derived(pqp_problem& P) { P.d = pqp_problem::Derived{}; }
 
 int problem_upload(pqp_problem& P, const float* qd, const float* fd, const float* md, const float* qp,
                    const float* qinv, const float* fp, const float* mp, const float* gp, const float* kp, int N, int M,
                    hipStream_t s) {
     if (P.Qd.p) {  // new data into an existing handle
-        PQP_HIP(hipStreamSynchronize(s));
+        PQP_HIP(hipStreamSynchronize(s));  // the captured graphs hold the derived buffers' addresses
         problem_reset_derived(P);
     }
     P.N = N;
     P.M = M;
     const size_t nn = (size_t)N * N, mm = (size_t)M * M, nm = (size_t)N * M;
     const size_t total = nn + N + 1 + 2 * mm + M + 1 + nm + N;
+    // small problems: every input through one pinned staging buffer, so the
+    // nine H2D copies are asynchronous DMA instead of pageable copies
+    float* h = nullptr;
     if (total <= (size_t)1 << 18) {
-        // small problems: every input through one pinned staging buffer, so
-        // the nine H2D copies are asynchronous DMA instead of pageable copies
-        if (P.hin_floats < total) {
-            if (P.hin) (void)hipHostFree(P.hin);
-            P.hin = nullptr;
-            P.hin_floats = 0;
-            PQP_HIP(hipHostMalloc((void**)&P.hin, sizeof(float) * total, hipHostMallocDefault));
-            P.hin_floats = total;
-        }
-        float* h = P.hin;
-        auto put = [&](DevBuf& d, const float* src, size_t n) -> int {
-            std::memcpy(h, src, sizeof(float) * n);
-            PQP_TRY(d.floats(n));
-            PQP_HIP(hipMemcpyAsync(d.p, h, sizeof(float) * n, hipMemcpyHostToDevice, s));
-            h += n;
-            return PQP_OK;
-        };
-        PQP_TRY(put(P.Qd, qd, nn));
-        PQP_TRY(put(P.Fd, fd, N));
-        PQP_TRY(put(P.Md, md, 1));
-        PQP_TRY(put(P.Qp, qp, mm));
-        PQP_TRY(put(P.Qinv, qinv, mm));
-        PQP_TRY(put(P.Fp, fp, M));
-        PQP_TRY(put(P.Mp, mp, 1));
-        PQP_TRY(put(P.Gp, gp, nm));
-        PQP_TRY(put(P.Kp, kp, N));
-        return problem_finish(P, s);
+        PQP_TRY(P.hin.reserve(sizeof(float) * total));
+        h = P.hin.f();
     }
-    PQP_TRY(upload(P.Qd, qd, (size_t)N * N, s));
-    PQP_TRY(upload(P.Fd, fd, N, s));
-    PQP_TRY(upload(P.Md, md, 1, s));
-    PQP_TRY(upload(P.Qp, qp, (size_t)M * M, s));
-    PQP_TRY(upload(P.Qinv, qinv, (size_t)M * M, s));
-    PQP_TRY(upload(P.Fp, fp, M, s));
-    PQP_TRY(upload(P.Mp, mp, 1, s));
-    PQP_TRY(upload(P.Gp, gp, (size_t)N * M, s));
-    PQP_TRY(upload(P.Kp, kp, N, s));
+    auto put = [&](DevBuf& d, const float* src, size_t n) -> int {
+        if (!h) return upload(d, src, n, s);
+        std::memcpy(h, src, sizeof(float) * n);
+        PQP_TRY(upload(d, h, n, s));
+        h += n;
+        return PQP_OK;
+    };
+    PQP_TRY(put(P.Qd, qd, nn));
+    PQP_TRY(put(P.Fd, fd, N));
+    PQP_TRY(put(P.Md, md, 1));
+    PQP_TRY(put(P.Qp, qp, mm));
+    PQP_TRY(put(P.Qinv, qinv, mm));
+    PQP_TRY(put(P.Fp, fp, M));
+    PQP_TRY(put(P.Mp, mp, 1));
+    PQP_TRY(put(P.Gp, gp, nm));
+    PQP_TRY(put(P.Kp, kp, N));
     return problem_finish(P, s);
 }
 
-// Run the persistent solve kernel until it reports Done/Capped.  Each launch
-// is bounded (chunk updates) so no launch runs unbounded.  `resume` = start
-// from P.Y instead of Y = 1000 (used by the terminate() drop-in, mode 2).
-// Fixed mode of a large problem: one multi-workgroup launch per update
-// (k_split_update), the stored split matrices built once per problem.
 // Lanes per workgroup of the relay update of an n_dual = N problem: row sides
 // of the stored split matrices, or rows of Qd for the lean relay.
 int pick_lw(int N) { return use_lean(N, N) ? lean_pick_lw(N) : split_pick_lw(N); }
 
-// The relay update's operand of the whole problem (rows 0..N-1), built on
-// first use (and rebuilt if lw or the layout changes): the stored split
-// matrices with lw row sides per workgroup, or, from n_dual >= g_tune.lean_min_n,
-// Qd itself with lw rows per workgroup (k_lean_relay, half the bytes).
-int ensure_split(pqp_problem& P, int lw, hipStream_t s) {
-    const int N = P.N;
-    const bool lean = use_lean(N, N);
-    if (P.SP.p && P.split_lw == lw && P.split_lean == lean) return PQP_OK;
-    if (split_lds_bytes(N) > kLdsBudget)
-        return set_error(PQP_ERR_ARG, "multi-workgroup solve: N=%d needs more than %zu B of LDS", N, kLdsBudget);
-    if (!P.theta.p) {  // small problems skip the large-path setup of problem_finish
-        PQP_TRY(P.theta.floats(N));
-        PQP_HIP(launch_theta_rows(P.Qd.f(), N, N, N, P.theta.f(), s));
-    }
-    PQP_TRY(P.Yb.floats(N));
-    if (!P.rerr.p) {
-        PQP_TRY(P.rerr.alloc(sizeof(int)));
-        PQP_HIP(hipMemsetAsync(P.rerr.p, 0, sizeof(int), s));
-    }
-    if (lean) {
-        PQP_TRY(P.SP.floats(lean_floats(N, N, lw)));
-        PQP_TRY(P.fdpn.floats(lean_aux_floats(N, N, lw)));
-        PQP_HIP(hipMemsetAsync(P.SP.p, 0, sizeof(float) * lean_floats(N, N, lw), s));
-        PQP_HIP(launch_build_lean(P.Qd.f(), N, P.theta.f(), P.Fd.f(), N, N, 0, lw, P.SP.f(), P.fdpn.f(), s));
-    } else {
-        PQP_TRY(P.SP.floats(split_floats(N, N, lw)));
-        PQP_TRY(P.fdpn.floats((size_t)2 * N));
-        PQP_HIP(hipMemsetAsync(P.SP.p, 0, sizeof(float) * split_floats(N, N, lw), s));
-        PQP_HIP(launch_build_split(P.Qd.f(), N, P.theta.f(), P.Fd.f(), N, N, 0, lw, P.SP.f(), P.fdpn.f(), s));
-    }
-    P.split_lw = lw;
-    P.split_lean = lean;
+// A block's sticky error word, made (and cleared) once.
+int relay_error_word(RelayBlock& b, hipStream_t s) {
+    if (b.err.p) return PQP_OK;
+    PQP_TRY(b.err.alloc(sizeof(int)));
+    PQP_HIP(hipMemsetAsync(b.err.p, 0, sizeof(int), s));
     return PQP_OK;
 }
 
+// Build the relay update's operand for rows row0 .. row0 + rows - 1 of an
+// n_dual = N problem from those rows of Qd (leading dimension ld) and their
+// theta: the stored split matrices with lw row sides per workgroup, or, for a
+// block of rows x N >= g_tune.lean_min_n^2 entries, the Qd rows themselves
+// with lw / 2 rows per workgroup (k_lean_relay, half the bytes).  By the
+// block's entries: the bytes the lean layout saves grow with rows x N, the
+// chain both layouts run with N alone.
+int relay_build(RelayBlock& b, const float* qd_rows, int ld, const float* theta, const float* Fd, int N, int rows,
+                int row0, int lw, hipStream_t s) {
+    PQP_TRY(relay_error_word(b, s));
+    const bool lean = use_lean(N, rows);
+    const size_t sp = lean ? lean_floats(N, rows, lw) : split_floats(N, rows, lw);
+    PQP_TRY(b.SP.floats(sp));
+    PQP_TRY(b.fdpn.floats(lean ? lean_aux_floats(N, rows, lw) : (size_t)2 * rows));
+    PQP_HIP(hipMemsetAsync(b.SP.p, 0, sizeof(float) * sp, s));
+    PQP_HIP((lean ? launch_build_lean : launch_build_split)(qd_rows, ld, theta, Fd, N, rows, row0, lw, b.SP.f(),
+                                                            b.fdpn.f(), s));
+    b.lw = lw;
+    b.lean = lean;
+    return PQP_OK;
+}
+
+// One relay update of a block's rows, Yin (N) -> Yout (rows), over the operand relay_build made.
+hipError_t relay_update(const RelayBlock& b, int N, int rows, int row0, const float* Yin, float* Yout, hipStream_t s,
+                        const int* gate = nullptr) {
+    return (b.lean ? launch_lean_update : launch_split_update)(b.SP.f(), b.fdpn.f(), N, rows, row0, b.lw, Yin, Yout, s,
+                                                               gate, static_cast<int*>(b.err.p));
+}
+
+// The relay update's operand of the whole problem (rows 0..N-1), built on
+// first use (and rebuilt if lw or the layout changes).
+int ensure_split(pqp_problem& P, int lw, hipStream_t s) {
+    const int N = P.N;
+    RelayBlock& b = P.d.relay.block;
+    if (b.SP.p && b.lw == lw && b.lean == use_lean(N, N)) return PQP_OK;
+    if (split_lds_bytes(N) > kLdsBudget)
+        return set_error(PQP_ERR_ARG, "multi-workgroup solve: N=%d needs more than %zu B of LDS", N, kLdsBudget);
+    PQP_TRY(ensure_theta(P, s));
+    PQP_TRY(P.d.Yb.floats(N));
+    return relay_build(b, P.Qd.f(), N, P.d.theta.f(), P.Fd.f(), N, N, 0, lw, s);
+}
+
 // One relay update of the whole problem, a -> b, over the operand ensure_split built.
-hipError_t problem_update(pqp_problem& P, int lw, const float* a, float* b, hipStream_t s, const int* gate = nullptr) {
-    int* err = static_cast<int*>(P.rerr.p);
-    return P.split_lean ? launch_lean_update(P.SP.f(), P.fdpn.f(), P.N, P.N, 0, lw, a, b, s, gate, err)
-                        : launch_split_update(P.SP.f(), P.fdpn.f(), P.N, P.N, 0, lw, a, b, s, gate, err);
+hipError_t problem_update(pqp_problem& P, const float* a, float* b, hipStream_t s, const int* gate = nullptr) {
+    return relay_update(P.d.relay.block, P.N, P.N, 0, a, b, s, gate);
 }
 
 // The relay kernels' sticky error word: read (the caller synchronizes s
@@ -510,61 +578,38 @@ int relay_error_check(DevBuf& word, int* host, hipStream_t s, const char* what) 
     return PQP_OK;
 }
 
-// Capture `n` dependent updates P.Y -> P.Yb -> P.Y ... into *exec (plus a
-// copy back into P.Y when n is odd).
-static int capture_updates(pqp_problem& P, int lw, long long n, hipGraphExec_t* exec, hipStream_t s) {
-    const int N = P.N;
-    if (*exec) {
-        (void)hipGraphExecDestroy(*exec);
-        *exec = nullptr;
-    }
-    hipGraph_t g = nullptr;
-    PQP_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    float* a = P.Y.f();
-    float* b = P.Yb.f();
-    hipError_t e = hipSuccess;
-    for (long long u = 0; u < n && e == hipSuccess; ++u) {
-        e = problem_update(P, lw, a, b, s);
-        std::swap(a, b);
-    }
-    if (e == hipSuccess && a != P.Y.f()) e = hipMemcpyAsync(P.Y.p, a, sizeof(float) * N, hipMemcpyDeviceToDevice, s);
-    const hipError_t e2 = hipStreamEndCapture(s, &g);
-    if (e != hipSuccess || e2 != hipSuccess) {
-        if (g) (void)hipGraphDestroy(g);
-        PQP_HIP(e != hipSuccess ? e : e2);
-    }
-    const hipError_t e3 = hipGraphInstantiate(exec, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    PQP_HIP(e3);
-    return PQP_OK;
+// Capture `n` dependent updates P.Y -> Yb -> P.Y ... into g (plus a copy back
+// into P.Y when n is odd).
+int capture_updates(pqp_problem& P, long long n, GraphExec& g, hipStream_t s) {
+    return g.capture(s, [&]() -> hipError_t {
+        float* a = P.Y.f();
+        float* b = P.d.Yb.f();
+        hipError_t e = hipSuccess;
+        for (long long u = 0; u < n && e == hipSuccess; ++u) {
+            e = problem_update(P, a, b, s);
+            std::swap(a, b);
+        }
+        if (e == hipSuccess && a != P.Y.f())
+            e = hipMemcpyAsync(P.Y.p, a, sizeof(float) * P.N, hipMemcpyDeviceToDevice, s);
+        return e;
+    });
 }
 
-// Fixed mode of a large problem: the relay update once per iteration, from
-// hipGraphs (per-update host launch overhead would otherwise exceed the
-// kernel itself): a chunk of kFixedChunk updates replayed as often as needed,
-// then a graph of the remainder.
-constexpr long long kFixedChunk = 256;  // even: a chunk starts and ends with the iterate in P.Y
-// Fixed mode of a problem with N <= persist_max_n(): every update in ONE
-// persistent launch (pqp_persist.hip), launches of at most kPersistChunk
-// updates chained through P.Y.
-constexpr long long kPersistChunk = 1 << 16;
 // The stored split matrices in the 32-lane layout (k_build_split), built once
 // per problem: the persistent fixed-mode launch and the persistent converge
 // launch's update role hold them in LDS.
 int ensure_persist_split(pqp_problem& P, hipStream_t s) {
     const int N = P.N;
-    if (P.SPp.p) return PQP_OK;
-    if (!P.theta.p) {
-        PQP_TRY(P.theta.floats(N));
-        PQP_HIP(launch_theta_rows(P.Qd.f(), N, N, N, P.theta.f(), s));
-    }
-    if (!P.Yb.p) PQP_TRY(P.Yb.floats(N));
-    PQP_TRY(P.SPp.floats(split_floats(N, N, 32)));
-    PQP_TRY(P.fdpnp.floats((size_t)2 * N));
-    PQP_HIP(hipMemsetAsync(P.SPp.p, 0, sizeof(float) * split_floats(N, N, 32), s));
-    PQP_HIP(launch_build_split(P.Qd.f(), N, P.theta.f(), P.Fd.f(), N, N, 0, 32, P.SPp.f(), P.fdpnp.f(), s));
-    PQP_TRY(P.gran.alloc(sizeof(unsigned long long) * 2 * N));
-    PQP_TRY(P.perr.alloc(sizeof(int)));
+    auto& ps = P.d.persist;
+    if (ps.SP.p) return PQP_OK;
+    PQP_TRY(ensure_theta(P, s));
+    PQP_TRY(P.d.Yb.floats(N));
+    PQP_TRY(ps.SP.floats(split_floats(N, N, 32)));
+    PQP_TRY(ps.fdpn.floats((size_t)2 * N));
+    PQP_HIP(hipMemsetAsync(ps.SP.p, 0, sizeof(float) * split_floats(N, N, 32), s));
+    PQP_HIP(launch_build_split(P.Qd.f(), N, P.d.theta.f(), P.Fd.f(), N, N, 0, 32, ps.SP.f(), ps.fdpn.f(), s));
+    PQP_TRY(ps.gran.alloc(sizeof(unsigned long long) * 2 * N));
+    PQP_TRY(ps.err.alloc(sizeof(int)));
     return PQP_OK;
 }
 
@@ -592,18 +637,36 @@ std::mutex& persist_lock() {
     return mu[dev >= 0 && dev < 64 ? dev : 0];
 }
 
+// What a solve reports, from the SolveState its last launch left.
+void report(const SolveState& st, SolveOut& out) {
+    out.h = st.h;
+    out.status = st.status;
+    out.have_costs = st.have_costs;
+    out.last_stop = st.last_stop;
+    if (st.have_costs) {
+        out.Jp = st.Jp;
+        out.Jd = st.Jd;
+    }
+}
+
+// Fixed mode of a problem with N <= persist_max_n(): every update in ONE
+// persistent launch (pqp_persist.hip), launches of at most kPersistChunk
+// updates chained through P.Y.
+constexpr long long kPersistChunk = 1 << 16;
 int problem_run_fixed_persist(pqp_problem& P, long long updates, SolveOut& out, hipStream_t s) {
     const int N = P.N;
     PQP_TRY(ensure_persist_split(P, s));
-    auto* gran = static_cast<unsigned long long*>(P.gran.p);
-    int* err = static_cast<int*>(P.perr.p);
+    auto& ps = P.d.persist;
+    float* Yb = P.d.Yb.f();
+    auto* gran = static_cast<unsigned long long*>(ps.gran.p);
+    int* err = static_cast<int*>(ps.err.p);
     PQP_HIP(launch_fill(P.Y.f(), 1000.0f, N, s));  // initMat(Y, 1000) :710
     std::lock_guard<std::mutex> one_at_a_time(persist_lock());
     for (long long done = 0; done < updates;) {
         const long long n = std::min(kPersistChunk, updates - done);
         // the launch reads its initial iterate from Yb while it writes P.Y
-        PQP_HIP(hipMemcpyAsync(P.Yb.p, P.Y.p, sizeof(float) * N, hipMemcpyDeviceToDevice, s));
-        PQP_HIP(launch_split_persist(P.SPp.f(), P.fdpnp.f(), N, (int)n, P.Yb.f(), P.Y.f(), gran, err, s));
+        PQP_HIP(hipMemcpyAsync(Yb, P.Y.p, sizeof(float) * N, hipMemcpyDeviceToDevice, s));
+        PQP_HIP(launch_split_persist(ps.SP.f(), ps.fdpn.f(), N, (int)n, Yb, P.Y.f(), gran, err, s));
         int herr = 0;
         PQP_HIP(hipMemcpyAsync(&herr, err, sizeof herr, hipMemcpyDeviceToHost, s));
         PQP_HIP(hipStreamSynchronize(s));
@@ -621,6 +684,11 @@ int problem_run_fixed_persist(pqp_problem& P, long long updates, SolveOut& out, 
     return PQP_OK;
 }
 
+// Fixed mode of a large problem: one multi-workgroup launch per update
+// (k_split_update / k_lean_relay), from hipGraphs (per-update host launch
+// overhead would otherwise exceed the kernel itself): a chunk of kFixedChunk
+// updates replayed as often as needed, then a graph of the remainder.
+constexpr long long kFixedChunk = 256;  // even: a chunk starts and ends with the iterate in P.Y
 int problem_run_fixed_split(pqp_problem& P, long long num_iter, SolveOut& out, hipStream_t s) {
     const int N = P.N;
     const long long updates = num_iter > 1 ? num_iter - 1 : 0;  // while(h < NUM_ITER)
@@ -634,45 +702,38 @@ int problem_run_fixed_split(pqp_problem& P, long long num_iter, SolveOut& out, h
     }
     const int lw = pick_lw(N);
     PQP_TRY(ensure_split(P, lw, s));
+    auto& R = P.d.relay;
     // every setting the captured launches bake in as an argument, the relay
     // wait budget's value included
     const long long variant = ((long long)lw << 8) | ((long long)use_lean(N, N) << 16) |
                               ((long long)(unsigned)g_tune.relay_spin_max << 24);
-    if (P.graph_variant != variant) {  // kernel selection changed: recapture both
-        P.graph_updates = -1;
-        P.chunk_ready = false;
-        P.graph_variant = variant;
+    if (R.graph_variant != variant) {  // kernel selection changed: recapture both
+        R.graph_updates = -1;
+        R.chunk_ready = false;
+        R.graph_variant = variant;
     }
     const long long full = updates / kFixedChunk, rem = updates % kFixedChunk;
-    if (full > 0 && !P.chunk_ready) {
-        PQP_TRY(capture_updates(P, lw, kFixedChunk, &P.chunk_graph, s));
-        P.chunk_ready = true;
+    if (full > 0 && !R.chunk_ready) {
+        PQP_TRY(capture_updates(P, kFixedChunk, R.chunk, s));
+        R.chunk_ready = true;
     }
-    if (rem > 0 && P.graph_updates != rem) {
-        PQP_TRY(capture_updates(P, lw, rem, &P.graph, s));
-        P.graph_updates = rem;
+    if (rem > 0 && R.graph_updates != rem) {
+        PQP_TRY(capture_updates(P, rem, R.rem, s));
+        R.graph_updates = rem;
     }
     PQP_HIP(launch_fill(P.Y.f(), 1000.0f, N, s));  // initMat(Y, 1000) :710
-    for (long long c = 0; c < full; ++c) PQP_HIP(hipGraphLaunch(P.chunk_graph, s));
-    if (rem > 0) PQP_HIP(hipGraphLaunch(P.graph, s));
+    for (long long c = 0; c < full; ++c) PQP_HIP(hipGraphLaunch(R.chunk.exec, s));
+    if (rem > 0) PQP_HIP(hipGraphLaunch(R.rem.exec, s));
     int herr = 0;
-    PQP_HIP(hipMemcpyAsync(&herr, P.rerr.p, sizeof herr, hipMemcpyDeviceToHost, s));
-    PQP_TRY(relay_error_check(P.rerr, &herr, s, "fixed-mode relay update"));
+    PQP_HIP(hipMemcpyAsync(&herr, R.block.err.p, sizeof herr, hipMemcpyDeviceToHost, s));
+    PQP_TRY(relay_error_check(R.block.err, &herr, s, "fixed-mode relay update"));
     out.h = updates + 1;
     out.status = kStatusDone;
     g_last_path = kPathFixedRelay;
     return PQP_OK;
 }
 
-// Converge mode of a large problem over many workgroups (pqp_wide.hip): one
-// iteration = terminate() as three multi-workgroup mat-vec launches and a
-// one-workgroup decision, then the relay update.  A chunk of kWideChunk
-// iterations is captured into a hipGraph and replayed until the device-side
-// status leaves Continue; launches after that point return at once.
-// Converge mode of a problem with N, M <= 1024 as ONE persistent launch
-// (pqp_converge.hip): the update and the stages of terminate() run as
-// concurrent roles, terminate(Y_u) beside the update to Y_{u+1}.  Launches
-// decide at most g_tune.converge_chunk iterates each and are chained through P.Y.
+// Whether converge mode of (N, M) runs as one persistent launch on this device.
 bool converge_persist_fits(int N, int M) {
     if (g_tune.converge_persist_off) return false;
     const int G = converge_persist_wgs(N, M, nullptr);
@@ -687,47 +748,52 @@ bool converge_persist_fits(int N, int M) {
     return (long long)converge_persist_per_cu(N, M) * cus >= G;
 }
 
+// Converge mode of a problem with N, M <= 1024 as ONE persistent launch
+// (pqp_converge.hip): the update and the stages of terminate() run as
+// concurrent roles, terminate(Y_u) beside the update to Y_{u+1}.  Launches
+// decide at most g_tune.converge_chunk iterates each and are chained through P.Y.
 int problem_run_converge_persist(pqp_problem& P, long long max_updates, SolveOut& out, hipStream_t s) {
     const int N = P.N, M = P.M;
     PQP_TRY(ensure_persist_split(P, s));
-    if (!P.CA1.p) {
+    auto& C = P.d.conv;
+    if (!C.A1.p) {
         const size_t n1 = converge_stage_floats(N, M, 1), n2 = converge_stage_floats(N, M, 2),
                      n3 = converge_stage_floats(N, M, 3);
-        PQP_TRY(P.CA1.floats(n1));
-        PQP_TRY(P.CA2.floats(n2));
-        PQP_TRY(P.CA3.floats(n3));
-        PQP_HIP(hipMemsetAsync(P.CA1.p, 0, sizeof(float) * n1, s));
-        PQP_HIP(hipMemsetAsync(P.CA2.p, 0, sizeof(float) * n2, s));
-        PQP_HIP(hipMemsetAsync(P.CA3.p, 0, sizeof(float) * n3, s));
-        PQP_HIP(launch_converge_pack(P.Qd.f(), P.Gp.f(), P.Qinv.f(), P.Qp.f(), N, M, P.CA1.f(), P.CA2.f(), P.CA3.f(),
-                                     s));
-        PQP_TRY(P.crings.alloc(sizeof(unsigned long long) * converge_ring_words(N, M)));
-        PQP_TRY(P.cwords.alloc(32));  // ctl, err (int), decided (long long)
+        PQP_TRY(C.A1.floats(n1));
+        PQP_TRY(C.A2.floats(n2));
+        PQP_TRY(C.A3.floats(n3));
+        PQP_HIP(hipMemsetAsync(C.A1.p, 0, sizeof(float) * n1, s));
+        PQP_HIP(hipMemsetAsync(C.A2.p, 0, sizeof(float) * n2, s));
+        PQP_HIP(hipMemsetAsync(C.A3.p, 0, sizeof(float) * n3, s));
+        PQP_HIP(launch_converge_pack(P.Qd.f(), P.Gp.f(), P.Qinv.f(), P.Qp.f(), N, M, C.A1.f(), C.A2.f(), C.A3.f(), s));
+        PQP_TRY(C.rings.alloc(sizeof(unsigned long long) * converge_ring_words(N, M)));
+        PQP_TRY(C.words.alloc(32));  // ctl, err (int), decided (long long)
     }
-    SolveState& st = *P.hst;
+    SolveState& st = *P.hst.as<SolveState>();
     st = SolveState{};
     st.h = 1;
     st.status = kStatusContinue;
     SolveState* dst = static_cast<SolveState*>(P.state.p);
     PQP_HIP(hipMemcpyAsync(dst, &st, sizeof st, hipMemcpyHostToDevice, s));
     PQP_HIP(launch_fill(P.Y.f(), 1000.0f, N, s));  // initMat(Y, 1000) :710
-    char* words = static_cast<char*>(P.cwords.p);
+    char* words = static_cast<char*>(C.words.p);
+    float* hio = P.hio.f();
     ConvergeLaunch L{};
     L.N = N;
     L.M = M;
     L.chunk = g_tune.converge_chunk;
     L.cap = max_updates;
-    L.SP = P.SPp.f();
-    L.A1 = P.CA1.f();
-    L.A2 = P.CA2.f();
-    L.A3 = P.CA3.f();
-    L.fdpn = P.fdpnp.f();
+    L.SP = P.d.persist.SP.f();
+    L.A1 = C.A1.f();
+    L.A2 = C.A2.f();
+    L.A3 = C.A3.f();
+    L.fdpn = P.d.persist.fdpn.f();
     L.Fp = P.Fp.f();
     L.Kp = P.Kp.f();
     L.Fd = P.Fd.f();
     L.Md = P.Md.f();
     L.Mp = P.Mp.f();
-    L.rings = P.crings.p;
+    L.rings = C.rings.p;
     L.st = dst;
     L.ctl = reinterpret_cast<int*>(words);
     L.err = reinterpret_cast<int*>(words + 4);
@@ -740,8 +806,8 @@ int problem_run_converge_persist(pqp_problem& P, long long max_updates, SolveOut
         PQP_HIP(launch_converge_persist(L, s));
         int herr = 0;
         // Y and U ride with the state readback (pinned staging, one sync)
-        PQP_HIP(hipMemcpyAsync(P.hio, P.Y.p, sizeof(float) * N, hipMemcpyDeviceToHost, s));
-        PQP_HIP(hipMemcpyAsync(P.hio + N, P.U.p, sizeof(float) * M, hipMemcpyDeviceToHost, s));
+        PQP_HIP(hipMemcpyAsync(hio, P.Y.p, sizeof(float) * N, hipMemcpyDeviceToHost, s));
+        PQP_HIP(hipMemcpyAsync(hio + N, P.U.p, sizeof(float) * M, hipMemcpyDeviceToHost, s));
         PQP_HIP(hipMemcpyAsync(&st, dst, sizeof st, hipMemcpyDeviceToHost, s));
         PQP_HIP(hipMemcpyAsync(&herr, L.err, sizeof herr, hipMemcpyDeviceToHost, s));
         PQP_HIP(hipStreamSynchronize(s));
@@ -754,18 +820,17 @@ int problem_run_converge_persist(pqp_problem& P, long long max_updates, SolveOut
         u0 = st.h - 1;  // the next launch starts from the iterate this one left in P.Y
     }
     out.staged = true;
-    out.h = st.h;
-    out.status = st.status;
-    out.have_costs = st.have_costs;
-    out.last_stop = 0;
+    report(st, out);
+    out.last_stop = 0;  // on purpose: this path reports no terminate() result, whatever the state holds
     g_last_path = kPathConvergePersist;
-    if (st.have_costs) {
-        out.Jp = st.Jp;
-        out.Jd = st.Jd;
-    }
     return PQP_OK;
 }
 
+// Converge mode of a large problem over many workgroups (pqp_wide.hip): one
+// iteration = terminate() as three multi-workgroup mat-vec launches and a
+// one-workgroup decision, then the relay update.  Chunks of iterations are
+// captured into hipGraphs and replayed until the device-side status leaves
+// Continue; launches after that point return at once.
 constexpr int kWideChunk = 16;      // even: each replay starts and ends with the iterate in P.Y
 constexpr int kWideFirstChunk = 2;  // the first replay of a solve
 int problem_run_wide(pqp_problem& P, long long max_updates, SolveOut& out, hipStream_t s, bool try_persist = true) {
@@ -777,30 +842,30 @@ int problem_run_wide(pqp_problem& P, long long max_updates, SolveOut& out, hipSt
     }
     const int lw = pick_lw(N);
     PQP_TRY(ensure_split(P, lw, s));
-    if (!P.QinvT.p) {
-        PQP_TRY(P.QinvT.floats((size_t)M * M));
-        PQP_TRY(P.GpT.floats((size_t)M * N));
-        PQP_TRY(P.tM.floats(M));
-        PQP_TRY(P.tq.floats(N));
-        PQP_TRY(P.tu.floats(M));
-        PQP_TRY(P.gu.floats(N));
-        PQP_TRY(P.wflag.alloc(sizeof(int)));
-        PQP_TRY(P.wcap.alloc(sizeof(long long)));
-        PQP_HIP(launch_transpose(P.Qinv.f(), M, M, P.QinvT.f(), s));  // QinvT[k][i] = Qp_inv[i][k]
-        PQP_HIP(launch_transpose(P.Gp.f(), N, M, P.GpT.f(), s));      // GpT[k][i] = Gp[i][k]
+    auto& W = P.d.wide;
+    if (!W.QinvT.p) {
+        PQP_TRY(W.QinvT.floats((size_t)M * M));
+        PQP_TRY(W.GpT.floats((size_t)M * N));
+        PQP_TRY(W.tM.floats(M));
+        PQP_TRY(W.tq.floats(N));
+        PQP_TRY(W.tu.floats(M));
+        PQP_TRY(W.gu.floats(N));
+        PQP_TRY(W.flag.alloc(sizeof(int)));
+        PQP_TRY(W.cap.alloc(sizeof(long long)));
+        PQP_HIP(launch_transpose(P.Qinv.f(), M, M, W.QinvT.f(), s));  // QinvT[k][i] = Qp_inv[i][k]
+        PQP_HIP(launch_transpose(P.Gp.f(), N, M, W.GpT.f(), s));      // GpT[k][i] = Gp[i][k]
     }
     SolveState* dst = static_cast<SolveState*>(P.state.p);
-    int* flag = static_cast<int*>(P.wflag.p);
-    long long* cap = static_cast<long long*>(P.wcap.p);
+    int* flag = static_cast<int*>(W.flag.p);
+    long long* cap = static_cast<long long*>(W.cap.p);
+    float* Yb = P.d.Yb.f();
+    DevBuf& rerr_word = P.d.relay.block.err;
+    int* rerr = static_cast<int*>(rerr_word.p);
     // every launch argument the capture bakes in (cap: a device word)
     const long long key = (long long)(((unsigned long long)(unsigned)g_tune.relay_spin_max << 32) |
                                       ((unsigned long long)use_lean(N, N) << 24) | (unsigned long long)(lw & 0xff));
-    int* rerr = static_cast<int*>(P.rerr.p);
-    if (!P.wgraph || P.wgraph_key != key) {
-        if (P.wgraph) {
-            (void)hipGraphExecDestroy(P.wgraph);
-            P.wgraph = nullptr;
-        }
+    if (W.key != key) {
+        W.key = -1;  // never a key's value: stays until all four chunks are captured
         // One iteration: terminate()'s launches, then the update, each gated on
         // the status word (once an iteration stops or hits the cap, the rest do
         // nothing).  The update on a forked graph branch beside terminate()
@@ -808,100 +873,68 @@ int problem_run_wide(pqp_problem& P, long long max_updates, SolveOut& out, hipSt
         auto iteration = [&](const float* cur, float* nxt) -> hipError_t {
             hipError_t e = hipSuccess;
             GemvJobs j1{};  // tmp = Gp'Y + Fp (computeUfromY :354-356) and Y'Qd (computeCost :652, Jd)
-            j1.job[0] = GemvJob{P.Gp.f(), cur, P.tM.f(), P.Fp.f(), M, N, M, kEpiAdd};
-            j1.job[1] = GemvJob{P.Qd.f(), cur, P.tq.f(), nullptr, N, N, N, kEpiPlain};
+            j1.job[0] = GemvJob{P.Gp.f(), cur, W.tM.f(), P.Fp.f(), M, N, M, kEpiAdd};
+            j1.job[1] = GemvJob{P.Qd.f(), cur, W.tq.f(), nullptr, N, N, N, kEpiPlain};
             j1.gate = &dst->status;
             j1.err = rerr;
             if ((e = launch_gemv_relay(j1, s)) != hipSuccess) return e;
             GemvJobs j2{};  // U = -(Qp_inv tmp) (:357-358)
-            j2.job[0] = GemvJob{P.QinvT.f(), P.tM.f(), P.U.f(), nullptr, M, M, M, kEpiNeg};
+            j2.job[0] = GemvJob{W.QinvT.f(), W.tM.f(), P.U.f(), nullptr, M, M, M, kEpiNeg};
             j2.gate = &dst->status;
             j2.err = rerr;
             if ((e = launch_gemv_relay(j2, s)) != hipSuccess) return e;
             GemvJobs j3{};  // checkFeas (:632-641) and U'Qp (computeCost, Jp)
-            j3.job[0] = GemvJob{P.GpT.f(), P.U.f(), P.gu.f(), P.Kp.f(), N, M, N, kEpiFeas};
-            j3.job[1] = GemvJob{P.Qp.f(), P.U.f(), P.tu.f(), nullptr, M, M, M, kEpiPlain};
+            j3.job[0] = GemvJob{W.GpT.f(), P.U.f(), W.gu.f(), P.Kp.f(), N, M, N, kEpiFeas};
+            j3.job[1] = GemvJob{P.Qp.f(), P.U.f(), W.tu.f(), nullptr, M, M, M, kEpiPlain};
             j3.gate = &dst->status;
             j3.flag = flag;
             j3.err = rerr;
             if ((e = launch_gemv_relay(j3, s)) != hipSuccess) return e;
-            const WideArgs w{dst, flag, P.tq.f(), P.tu.f(), cur, P.U.f(), P.Fd.f(), P.Fp.f(), P.Md.f(), P.Mp.f(),
+            const WideArgs w{dst, flag, W.tq.f(), W.tu.f(), cur, P.U.f(), P.Fd.f(), P.Fp.f(), P.Md.f(), P.Mp.f(),
                              N, M, cap};
             if ((e = launch_wide_decide(w, s)) != hipSuccess) return e;
-            return problem_update(P, lw, cur, nxt, s, &dst->status);
+            return problem_update(P, cur, nxt, s, &dst->status);
         };
         // replays of 2, 2, 4, 8, then kWideChunk iterations: a solve that stops
         // early launches at most about as many no-op iterations as it ran
-        auto capture = [&](int iters, hipGraphExec_t* exec) -> int {
-            hipGraph_t g = nullptr;
-            PQP_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-            hipError_t e = hipSuccess;
-            for (int it = 0; it < iters && e == hipSuccess; it += 2) {
-                e = iteration(P.Y.f(), P.Yb.f());
-                if (e == hipSuccess) e = iteration(P.Yb.f(), P.Y.f());
-            }
-            const hipError_t e2 = hipStreamEndCapture(s, &g);
-            if (e != hipSuccess || e2 != hipSuccess) {
-                if (g) (void)hipGraphDestroy(g);
-                PQP_HIP(e != hipSuccess ? e : e2);
-            }
-            const hipError_t e3 = hipGraphInstantiate(exec, g, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(g);
-            PQP_HIP(e3);
-            return PQP_OK;
+        auto capture = [&](int iters, GraphExec& g) -> int {
+            return g.capture(s, [&]() -> hipError_t {
+                hipError_t e = hipSuccess;
+                for (int it = 0; it < iters && e == hipSuccess; it += 2) {
+                    e = iteration(P.Y.f(), Yb);
+                    if (e == hipSuccess) e = iteration(Yb, P.Y.f());
+                }
+                return e;
+            });
         };
-        for (hipGraphExec_t* g : {&P.wgraph_first, &P.wgraph4, &P.wgraph8})
-            if (*g) {
-                (void)hipGraphExecDestroy(*g);
-                *g = nullptr;
-            }
-        PQP_TRY(capture(kWideFirstChunk, &P.wgraph_first));
-        PQP_TRY(capture(4, &P.wgraph4));
-        PQP_TRY(capture(8, &P.wgraph8));
-        PQP_TRY(capture(kWideChunk, &P.wgraph));
-        P.wgraph_key = key;
+        PQP_TRY(capture(kWideFirstChunk, W.first));
+        PQP_TRY(capture(4, W.g4));
+        PQP_TRY(capture(8, W.g8));
+        PQP_TRY(capture(kWideChunk, W.full));
+        W.key = key;
     }
     PQP_HIP(launch_wide_init(dst, flag, cap, max_updates, P.Y.f(), N, s));
-    SolveState& st = *P.hst;
+    SolveState& st = *P.hst.as<SolveState>();
     for (int launch = 0;; ++launch) {
-        hipGraphExec_t g = launch < 2 ? P.wgraph_first : (launch == 2 ? P.wgraph4 : (launch == 3 ? P.wgraph8 : P.wgraph));
-        PQP_HIP(hipGraphLaunch(g, s));
+        const GraphExec& g = launch < 2 ? W.first : (launch == 2 ? W.g4 : (launch == 3 ? W.g8 : W.full));
+        PQP_HIP(hipGraphLaunch(g.exec, s));
         PQP_HIP(hipMemcpyAsync(&st, dst, sizeof st, hipMemcpyDeviceToHost, s));
         PQP_HIP(hipStreamSynchronize(s));
         if (st.status != kStatusContinue) break;
     }
     if ((st.h - 1) & 1)  // odd number of updates: the iterate is in Yb
-        PQP_HIP(hipMemcpyAsync(P.Y.p, P.Yb.p, sizeof(float) * N, hipMemcpyDeviceToDevice, s));
+        PQP_HIP(hipMemcpyAsync(P.Y.p, Yb, sizeof(float) * N, hipMemcpyDeviceToDevice, s));
     int herr = 0;
     PQP_HIP(hipMemcpyAsync(&herr, rerr, sizeof herr, hipMemcpyDeviceToHost, s));
-    PQP_TRY(relay_error_check(P.rerr, &herr, s, "converge-mode relay chain"));
+    PQP_TRY(relay_error_check(rerr_word, &herr, s, "converge-mode relay chain"));
     g_last_path = kPathConvergeWide;
-    out.h = st.h;
-    out.status = st.status;
-    out.have_costs = st.have_costs;
-    out.last_stop = st.last_stop;
-    if (st.have_costs) {
-        out.Jp = st.Jp;
-        out.Jd = st.Jd;
-    }
+    report(st, out);
     return PQP_OK;
 }
 
-// One small problem (N, M <= 32) from Y = 1000 in ONE launch (pqp_tiny.hip:
-// k_fixed_one / k_solve_quintet): the kernel starts from h = 1 itself (no state
-// upload) and writes Y, U, the state and its error word to pinned host memory,
-// so a solve is one launch and one synchronisation, no copy kernels.
-int problem_run_tiny(pqp_problem& P, int mode, long long num_iter, long long max_updates, SolveOut& out,
-                     hipStream_t s) {
-    const int N = P.N, M = P.M;
-    if (!P.hout) {
-        // fine-grained (coherent) host memory: the kernel's stores reach it
-        // without a cache write-back at the kernel's end
-        PQP_HIP(hipHostMalloc((void**)&P.hout, sizeof(float) * kTinyOutFloats,
-                              hipHostMallocMapped | hipHostMallocCoherent));
-        PQP_HIP(hipHostGetDevicePointer(&P.hout_dev, P.hout, 0));
-        std::memset(P.hout, 0, sizeof(float) * kTinyOutFloats);  // tag 0: no launch's
-    }
+// The SolveArgs fields every one-workgroup solve of a handle shares; the
+// caller adds its own (QdT, theta, chunk; the one-launch tiny solve's output).
+SolveArgs solve_args(const pqp_problem& P, int mode, long long num_iter, long long max_updates) {
     SolveArgs a{};
     a.Qd = P.Qd.f();
     a.Fd = P.Fd.f();
@@ -914,28 +947,43 @@ int problem_run_tiny(pqp_problem& P, int mode, long long num_iter, long long max
     a.Kp = P.Kp.f();
     a.Y = P.Y.f();
     a.U = P.U.f();
-    a.N = N;
-    a.M = M;
-    a.ldq = round4(N);
-    a.ldm = round4(M);
+    a.N = P.N;
+    a.M = P.M;
+    a.ldq = round4(P.N);
+    a.ldm = round4(P.M);
     a.mode = mode;
     a.num_iter = num_iter;
     a.max_updates = max_updates;
-    // iterates per launch: about 2^26 element updates (28.5 k at the bundled
-    // size, so its solves stay one launch), bounded so that a long fixed-mode
-    // solve or an uncapped converge solve is a sequence of launches that
-    // resume from the device state, not one kernel running for minutes
-    // (ADVICE r5); the tiny_chunk knob sets it for the resume tests
-    const double per_update = 3.0 * N * N + 2.0 * N * M + 2.0 * M * M + 1.0;
-    a.chunk = g_tune.tiny_chunk > 0 ? g_tune.tiny_chunk : std::max(1024LL, (long long)((1 << 26) / per_update));
+    return a;
+}
+
+// One small problem (N, M <= 32) from Y = 1000 in ONE launch (pqp_tiny.hip:
+// k_fixed_one / k_solve_quintet): the kernel starts from h = 1 itself (no state
+// upload) and writes Y, U, the state and its error word to pinned host memory,
+// so a solve is one launch and one synchronisation, no copy kernels.
+int problem_run_tiny(pqp_problem& P, int mode, long long num_iter, long long max_updates, SolveOut& out,
+                     hipStream_t s) {
+    const int N = P.N, M = P.M;
+    if (!P.hout.p) {
+        // fine-grained (coherent) host memory: the kernel's stores reach it
+        // without a cache write-back at the kernel's end
+        PQP_TRY(P.hout.reserve(sizeof(float) * kTinyOutFloats, hipHostMallocMapped | hipHostMallocCoherent));
+        std::memset(P.hout.p, 0, sizeof(float) * kTinyOutFloats);  // tag 0: no launch's
+    }
+    float* hout = P.hout.f();
+    SolveArgs a = solve_args(P, mode, num_iter, max_updates);
+    // about 2^26 element updates per launch (28.5 k iterates at the bundled
+    // size, so its solves stay one launch); the tiny_chunk knob sets it for
+    // the resume tests
+    a.chunk = g_tune.tiny_chunk > 0 ? g_tune.tiny_chunk : updates_per_launch(N, M, 1 << 26, 1024);
     a.fresh = 1;
-    a.hout = P.hout_dev;
+    a.hout = P.hout.dev;
     a.tiny_flags = (g_tune.tiny_dense ? kTinyDense : 0) | (g_tune.tiny_stall ? kTinyStall : 0);
     a.trace = g_tune.tiny_trace;  // k_solve_quintet timing (bundled size only): 4 words per wave
     SolveState* dst = static_cast<SolveState*>(P.state.p);
-    const SolveState* hs = reinterpret_cast<const SolveState*>(P.hout + kTinyOutStateOffset);
-    const int* herr = reinterpret_cast<const int*>(P.hout) + kTinyOutErrOffset;
-    volatile const int* htag = reinterpret_cast<const int*>(P.hout) + kTinyOutTagOffset;
+    const SolveState* hs = reinterpret_cast<const SolveState*>(hout + kTinyOutStateOffset);
+    const int* herr = reinterpret_cast<const int*>(hout) + kTinyOutErrOffset;
+    volatile const int* htag = reinterpret_cast<const int*>(hout) + kTinyOutTagOffset;
     for (;;) {
         P.out_tag = (P.out_tag + 1) & 0x7fffffffu;  // positive, never 0 (the zeroed buffer's tag)
         if (P.out_tag == 0) P.out_tag = 1;
@@ -949,11 +997,11 @@ int problem_run_tiny(pqp_problem& P, int mode, long long num_iter, long long max
             // knob forces this path in tests): read the device copies instead --
             // Y, U, the state and the error word behind it
             ++g_tiny_stale;
-            PQP_HIP(hipMemcpyAsync(P.hout, P.Y.p, sizeof(float) * N, hipMemcpyDeviceToHost, s));
+            PQP_HIP(hipMemcpyAsync(hout, P.Y.p, sizeof(float) * N, hipMemcpyDeviceToHost, s));
             if (mode == kModeConverge)
-                PQP_HIP(hipMemcpyAsync(P.hout + kTinyOutUOffset, P.U.p, sizeof(float) * M, hipMemcpyDeviceToHost, s));
-            PQP_HIP(hipMemcpyAsync(P.hout + kTinyOutStateOffset, dst, sizeof(SolveState), hipMemcpyDeviceToHost, s));
-            PQP_HIP(hipMemcpyAsync(P.hout + kTinyOutErrOffset, reinterpret_cast<const char*>(dst) + kTinyDevErr,
+                PQP_HIP(hipMemcpyAsync(hout + kTinyOutUOffset, P.U.p, sizeof(float) * M, hipMemcpyDeviceToHost, s));
+            PQP_HIP(hipMemcpyAsync(hout + kTinyOutStateOffset, dst, sizeof(SolveState), hipMemcpyDeviceToHost, s));
+            PQP_HIP(hipMemcpyAsync(hout + kTinyOutErrOffset, reinterpret_cast<const char*>(dst) + kTinyDevErr,
                                    sizeof(int), hipMemcpyDeviceToHost, s));
             PQP_HIP(hipStreamSynchronize(s));
         }
@@ -961,21 +1009,19 @@ int problem_run_tiny(pqp_problem& P, int mode, long long num_iter, long long max
         if (hs->status != kStatusContinue) break;
         a.fresh = 0;  // (a chunk ran out) resume from the device state
     }
-    std::memcpy(P.hio, P.hout, sizeof(float) * N);
-    if (mode == kModeConverge) std::memcpy(P.hio + N, P.hout + kTinyOutUOffset, sizeof(float) * M);
+    std::memcpy(P.hio.p, hout, sizeof(float) * N);
+    if (mode == kModeConverge) std::memcpy(P.hio.f() + N, hout + kTinyOutUOffset, sizeof(float) * M);
     out.staged = true;
-    out.h = hs->h;
-    out.status = hs->status;
-    out.have_costs = hs->have_costs;
-    out.last_stop = hs->last_stop;
-    if (hs->have_costs) {
-        out.Jp = hs->Jp;
-        out.Jd = hs->Jd;
-    }
+    report(*hs, out);
     g_last_path = kPathOneWorkgroup;
     return PQP_OK;
 }
 
+// Route a solve to its path; the rest of this function is the one-workgroup
+// solver (k_solve_tiny / _small / _single) run until it reports Done/Capped.
+// Each launch is bounded (chunk updates) so no launch runs unbounded.
+// `resume` = start from P.Y instead of Y = 1000 (used by the terminate()
+// drop-in, mode 2).
 int problem_run(pqp_problem& P, int mode, long long num_iter, long long max_updates, bool resume, SolveOut& out,
                 hipStream_t s) {
     const int N = P.N, M = P.M;
@@ -999,36 +1045,17 @@ int problem_run(pqp_problem& P, int mode, long long num_iter, long long max_upda
         (mode == kModeFixed || (mode == kModeConverge && N + M < 64)))
         return problem_run_tiny(P, mode, num_iter, max_updates, out, s);
     if (!P.small) PQP_TRY(ensure_single(P, s));
-    SolveState& st = *P.hst;
+    SolveState& st = *P.hst.as<SolveState>();
     st = SolveState{};
     st.h = 1;
     st.resume = resume ? 1 : 0;
     PQP_HIP(hipMemcpyAsync(P.state.p, &st, sizeof st, hipMemcpyHostToDevice, s));
-    SolveArgs a{};
-    a.QdT = P.QdT.f();
-    a.Qd = P.Qd.f();
-    a.theta = P.theta.f();
-    a.Fd = P.Fd.f();
-    a.Md = P.Md.f();
-    a.Qp = P.Qp.f();
-    a.Qinv = P.Qinv.f();
-    a.Fp = P.Fp.f();
-    a.Mp = P.Mp.f();
-    a.Gp = P.Gp.f();
-    a.Kp = P.Kp.f();
-    a.Y = P.Y.f();
-    a.U = P.U.f();
-    a.N = N;
-    a.M = M;
-    a.ldq = round4(N);
-    a.ldm = round4(M);
-    a.mode = mode;
-    a.num_iter = num_iter;
-    a.max_updates = max_updates;
-    const double per_update = (double)N * N * 3.0 + 2.0 * N * M + 2.0 * M * M + 1.0;
-    const long long chunk = (long long)((double)(1 << 26) / per_update);
-    a.chunk = chunk < 1 ? 1 : chunk;
+    SolveArgs a = solve_args(P, mode, num_iter, max_updates);
+    a.QdT = P.d.QdT.f();
+    a.theta = P.d.theta.f();
+    a.chunk = updates_per_launch(N, M, 1 << 26, 1);
     SolveState* dst = static_cast<SolveState*>(P.state.p);
+    float* hio = P.hio.f();
     for (;;) {
         if (P.N <= 32 && P.M <= 32 && !g_tune.force_small)
             PQP_HIP(launch_solve_tiny(a, dst, s));
@@ -1038,22 +1065,15 @@ int problem_run(pqp_problem& P, int mode, long long num_iter, long long max_upda
             PQP_HIP(launch_solve_single(a, dst, s));
         // Y and U ride with the state readback (pinned, one sync per launch);
         // the copies of the launch that finishes are the ones that stand
-        PQP_HIP(hipMemcpyAsync(P.hio, P.Y.p, sizeof(float) * N, hipMemcpyDeviceToHost, s));
-        PQP_HIP(hipMemcpyAsync(P.hio + N, P.U.p, sizeof(float) * M, hipMemcpyDeviceToHost, s));
+        PQP_HIP(hipMemcpyAsync(hio, P.Y.p, sizeof(float) * N, hipMemcpyDeviceToHost, s));
+        PQP_HIP(hipMemcpyAsync(hio + N, P.U.p, sizeof(float) * M, hipMemcpyDeviceToHost, s));
         PQP_HIP(hipMemcpyAsync(&st, dst, sizeof st, hipMemcpyDeviceToHost, s));
         PQP_HIP(hipStreamSynchronize(s));
         if (st.status != kStatusContinue) break;
     }
     out.staged = true;
-    out.h = st.h;
-    out.status = st.status;
-    out.have_costs = st.have_costs;
-    out.last_stop = st.last_stop;
+    report(st, out);
     g_last_path = kPathOneWorkgroup;
-    if (st.have_costs) {
-        out.Jp = st.Jp;
-        out.Jd = st.Jd;
-    }
     return PQP_OK;
 }
 
@@ -1136,13 +1156,14 @@ int pqp_problem_solve(pqp_problem* P, int mode, long long num_iter, long long ma
     PQP_TRY(problem_run(*P, mode == PQP_MODE_CONVERGE ? kModeConverge : kModeFixed, num_iter, max_updates, false, o,
                         s));
     const bool want_u = U && mode == PQP_MODE_CONVERGE;
+    float* hio = P->hio.f();
     if (!o.staged) {  // through the pinned staging buffer: one sync, no pageable DMA
-        PQP_HIP(hipMemcpyAsync(P->hio, P->Y.p, sizeof(float) * P->N, hipMemcpyDeviceToHost, s));
-        if (want_u) PQP_HIP(hipMemcpyAsync(P->hio + P->N, P->U.p, sizeof(float) * P->M, hipMemcpyDeviceToHost, s));
+        PQP_HIP(hipMemcpyAsync(hio, P->Y.p, sizeof(float) * P->N, hipMemcpyDeviceToHost, s));
+        if (want_u) PQP_HIP(hipMemcpyAsync(hio + P->N, P->U.p, sizeof(float) * P->M, hipMemcpyDeviceToHost, s));
         PQP_HIP(hipStreamSynchronize(s));
     }
-    std::memcpy(Y, P->hio, sizeof(float) * P->N);
-    if (want_u) std::memcpy(U, P->hio + P->N, sizeof(float) * P->M);
+    std::memcpy(Y, hio, sizeof(float) * P->N);
+    if (want_u) std::memcpy(U, hio + P->N, sizeof(float) * P->M);
     if (h_out) *h_out = o.h;
     if (Jp_out) *Jp_out = o.Jp;
     if (Jd_out) *Jd_out = o.Jd;
@@ -1258,9 +1279,9 @@ int pqp_run_example(const char* dir, void* out_file) {
     PQP_TRY(P.Md.floats(1));
     PQP_TRY(Jp.floats(1));
     PQP_TRY(Jd.floats(1));
-    std::swap(P.Qinv.p, Qinv.p);
-    std::swap(P.Gp.p, Gp.p);
-    std::swap(P.Kp.p, Kp.p);
+    P.Qinv = std::move(Qinv);
+    P.Gp = std::move(Gp);
+    P.Kp = std::move(Kp);
     PQP_TRY(dev_gauss_jordan(P.Qp.f(), P.Qinv.f(), M, s));                                                // :989
     PQP_TRY(dev_compute_fp(P.Fp.f(), Fp1.f(), Fp2.f(), Fp3.f(), D.f(), x.f(), m, nd, ns, s));            // :991
     PQP_TRY(dev_compute_mp(P.Mp.f(), Mp1.f(), Mp2.f(), Mp3.f(), Mp4.f(), Mp5.f(), Mp6.f(), D.f(), x.f(), nd, ns,
@@ -1380,30 +1401,13 @@ int pqp_rowblock_create(const float* d_Qd_rows, int ld, const float* d_Fd, int N
     b->N = N;
     b->row0 = row0;
     b->rows = rows;
-    PQP_TRY(b->err.alloc(sizeof(int)));
-    PQP_HIP(hipMemsetAsync(b->err.p, 0, sizeof(int), s));
+    PQP_TRY(relay_error_word(b->relay, s));  // all an empty block holds
     if (rows > 0) {
         DevBuf theta;
         PQP_TRY(theta.floats(rows));
-        // by the block's entries: the bytes the lean layout saves grow with
-        // rows x N, the chain both layouts run with N alone
-        b->lean = use_lean(N, rows);
         PQP_HIP(launch_theta_rows(d_Qd_rows, ld, N, rows, theta.f(), s));
-        if (b->lean) {  // Qd rows themselves (k_lean_relay): half the bytes of the split matrices
-            b->lw = lean_pick_lw(rows);
-            PQP_TRY(b->SP.floats(lean_floats(N, rows, b->lw)));
-            PQP_TRY(b->fdpn.floats(lean_aux_floats(N, rows, b->lw)));
-            PQP_HIP(hipMemsetAsync(b->SP.p, 0, sizeof(float) * lean_floats(N, rows, b->lw), s));
-            PQP_HIP(launch_build_lean(d_Qd_rows, ld, theta.f(), d_Fd, N, rows, row0, b->lw, b->SP.f(), b->fdpn.f(),
-                                      s));
-        } else {
-            b->lw = split_pick_lw(rows);
-            PQP_TRY(b->SP.floats(split_floats(N, rows, b->lw)));
-            PQP_TRY(b->fdpn.floats((size_t)2 * rows));
-            PQP_HIP(hipMemsetAsync(b->SP.p, 0, sizeof(float) * split_floats(N, rows, b->lw), s));
-            PQP_HIP(launch_build_split(d_Qd_rows, ld, theta.f(), d_Fd, N, rows, row0, b->lw, b->SP.f(),
-                                       b->fdpn.f(), s));
-        }
+        const int lw = use_lean(N, rows) ? lean_pick_lw(rows) : split_pick_lw(rows);
+        PQP_TRY(relay_build(b->relay, d_Qd_rows, ld, theta.f(), d_Fd, N, rows, row0, lw, s));
         PQP_HIP(hipStreamSynchronize(s));  // theta is freed on return
     }
     *out = b.release();
@@ -1414,12 +1418,7 @@ int pqp_rowblock_update(pqp_rowblock* b, const float* d_Y, float* d_Y_rows, void
     if (!b || !d_Y || (b->rows > 0 && !d_Y_rows)) return set_error(PQP_ERR_ARG, "pqp_rowblock_update: null argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
     DeviceGuard on(b->dev);
-    int* err = static_cast<int*>(b->err.p);
-    if (b->lean)
-        PQP_HIP(launch_lean_update(b->SP.f(), b->fdpn.f(), b->N, b->rows, b->row0, b->lw, d_Y, d_Y_rows, s, nullptr, err));
-    else
-        PQP_HIP(launch_split_update(b->SP.f(), b->fdpn.f(), b->N, b->rows, b->row0, b->lw, d_Y, d_Y_rows, s, nullptr,
-                                    err));
+    PQP_HIP(relay_update(b->relay, b->N, b->rows, b->row0, d_Y, d_Y_rows, s));
     return PQP_OK;
 }
 
@@ -1428,8 +1427,8 @@ int pqp_rowblock_check(pqp_rowblock* b, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     DeviceGuard on(b->dev);
     int herr = 0;
-    PQP_HIP(hipMemcpyAsync(&herr, b->err.p, sizeof herr, hipMemcpyDeviceToHost, s));
-    return relay_error_check(b->err, &herr, s, "pqp_rowblock_update");
+    PQP_HIP(hipMemcpyAsync(&herr, b->relay.err.p, sizeof herr, hipMemcpyDeviceToHost, s));
+    return relay_error_check(b->relay.err, &herr, s, "pqp_rowblock_update");
 }
 
 int pqp_rowblock_destroy(pqp_rowblock* b) {
@@ -2085,10 +2084,7 @@ namespace pqp {
 // quarter (infeasible) to 1.4 (feasible) iterates at 2^26:
 // profiles/r04/pipe/launch_amortization.json), or the batch_chunk knob
 long long batch_chunk_for(int N, int M) {
-    if (g_tune.batch_chunk > 0) return g_tune.batch_chunk;
-    const double per_update = (double)N * N * 3.0 + 2.0 * N * M + 2.0 * M * M + 1.0;
-    const long long chunk = (long long)((double)(1 << 28) / per_update);
-    return chunk < 1 ? 1 : chunk;
+    return g_tune.batch_chunk > 0 ? g_tune.batch_chunk : updates_per_launch(N, M, 1 << 28, 1);
 }
 }  // namespace pqp
 

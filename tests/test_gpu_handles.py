@@ -64,6 +64,67 @@ def test_concurrent_handles_from_threads(gpu_lib, orc):
         p.close()
 
 
+def test_one_handle_through_every_path(gpu_lib, orc):
+    """ONE handle through all five solver paths in turn (n_dual 160: past the
+    k_solve_small LDS budget, under both persistent limits and under
+    wide_min_n), so the paths meet each other's derived state: the shared theta
+    and second iterate, the graph cache keys, QdT built late.  Every result is
+    bit-identical to the oracle, and the defaults give the same bits at the end
+    as at the start."""
+    P = orc.synth_problem(3, 1, 160, 80)
+    N = P["N"]
+    want_fixed, Y, done = {}, None, 0
+    for num_iter in (45, 300, 600):  # one oracle run, continued
+        Y = orc.iterate(P["Qd"], P["Fd"], N, num_iter - 1 - done, Y0=Y)
+        want_fixed[num_iter], done = Y, num_iter - 1
+    want_conv = {cap: orc.solve(P, max_updates=cap) for cap in (7, 8)}
+    old = {}
+
+    def tune(key, value):
+        old.setdefault(key, gpu_lib.tune(key, value))
+
+    def fixed(prob, num_iter, path):
+        r = prob.solve(mode=1, num_iter=num_iter)
+        assert gpu_lib.tune_get("last_path") == path, (num_iter, gpu_lib.tune_get("last_path"))
+        assert_bitwise(r["Y"], want_fixed[num_iter], f"path {path}, num_iter {num_iter}: Y")
+        return r
+
+    def converge(prob, cap, path):
+        h, Yc, Uc = want_conv[cap]
+        r = prob.solve(max_updates=cap)
+        assert gpu_lib.tune_get("last_path") == path, (cap, gpu_lib.tune_get("last_path"))
+        assert r["h"] == abs(h), (path, cap, r["h"], h)
+        assert_bitwise(r["Y"], Yc, f"path {path}, cap {cap}: Y")
+        assert_bitwise(r["U"], Uc, f"path {path}, cap {cap}: U")
+        return r
+
+    with gpu_lib.Problem(P) as prob:
+        try:
+            first = fixed(prob, 300, 1), converge(prob, 8, 3)
+            tune("persist_off", 1)
+            fixed(prob, 300, 2)  # one chunk of 256 and a remainder of 43
+            fixed(prob, 45, 2)   # a remainder of 44 alone: recaptured, the chunk graph kept
+            fixed(prob, 600, 2)  # two chunks and a remainder of 87
+            tune("relay_spin_max", 1 << 19)  # another variant: both graphs recaptured
+            fixed(prob, 300, 2)
+            tune("converge_persist_off", 1)
+            tune("wide_min_n", 0)
+            converge(prob, 7, 4)  # an odd, then an even number of updates: the
+            converge(prob, 8, 4)  # iterate ends in either ping-pong buffer
+            gpu_lib.tune("wide_min_n", old["wide_min_n"])
+            converge(prob, 8, 5)  # k_solve_single: QdT is built only now
+            for key, value in old.items():
+                gpu_lib.tune(key, value)
+            again = fixed(prob, 300, 1), converge(prob, 8, 3)
+        finally:
+            for key, value in old.items():
+                gpu_lib.tune(key, value)
+    assert_bitwise(again[0]["Y"], first[0]["Y"], "defaults again, fixed mode: Y")
+    assert again[1]["h"] == first[1]["h"]
+    assert_bitwise(again[1]["Y"], first[1]["Y"], "defaults again, converge mode: Y")
+    assert_bitwise(again[1]["U"], first[1]["U"], "defaults again, converge mode: U")
+
+
 def test_two_threads_one_handle_serialize(gpu_lib, orc):
     """Calls on ONE handle from two threads are serialized by its lock: both
     get the oracle's result."""
