@@ -355,6 +355,62 @@ int pqp_rowblock_destroy(pqp_rowblock *b);
 int pqp_synth_rows(uint32_t seed, long long inst, int N, int M, int row0, int rows, float *d_Qd_rows, int ld,
                    float *d_Fd, float *d_Md, void *stream);
 
+/* ----------------------------------------------------------------------
+ * 2e. Receding-horizon re-solve: the NEXT control step of a resident problem.
+ * Between two steps of linear MPC only the measured state (and perhaps the
+ * bounds Kp) changes: that moves Fp and Mp, and through them Fd = (Gp Qp_inv)
+ * Fp + Kp and Md = (Fp' Qp_inv) Fp - Mp (PQP_CPU.c:456-479).  Qd, Theta, the
+ * packed matrices and the captured graphs stay.
+ *
+ * Warm start, everywhere below: the solve is solveQuadraticDual with line :710
+ * (initMat(Y, 1000)) replaced by Y = Y0 and nothing else changed -- h still
+ * starts at 1, converge mode calls terminate(Y0) before the first update,
+ * fixed mode runs num_iter - 1 updates from Y0.  Y0 is taken as given: no
+ * clamping, no validation of sign or finiteness.  The update is
+ * multiplicative, so an entry of Y0 that is exactly 0 stays 0 for the whole
+ * solve ("Receding-horizon re-solve").
+ * -------------------------------------------------------------------- */
+
+/* New linear terms for a resident problem: uploads Fp (M), Mp (1) and, when
+ * not NULL, Kp (N); recomputes Fd and Md on the device exactly as
+ * convertToDual would (PQP_CPU.c:456-479, :491-492; NaN operands: as
+ * convertToDual above) and refreshes, in place, everything the solve paths
+ * derived from Fd.  Qd, Theta, packed matrices and captured graphs are kept.
+ * The first call on a problem also builds Gp Qp_inv (N x M), once. */
+int pqp_problem_update_linear(pqp_problem *p, const float *Fp, const float *Mp, const float *Kp);
+/* The handle's current Fd (N) and Md (1); either may be NULL. */
+int pqp_problem_get_dual(pqp_problem *p, float *Fd, float *Md);
+#define PQP_START_COLD 0 /* Y = 1000: identical to pqp_problem_solve                       */
+#define PQP_START_HOST 1 /* Y = Y0 (N host floats)                                           */
+#define PQP_START_LAST 2 /* Y = the final iterate of this handle's previous solve (device-resident, no
+                            upload); PQP_ERR_ARG if the handle has not solved yet */
+/* pqp_problem_solve from a chosen start; a warm solve takes the same solver
+ * path as a cold solve of the same shape and mode. */
+int pqp_problem_solve_from(pqp_problem *p, int start, const float *Y0, int mode, long long num_iter,
+                           long long max_updates, float *Y, float *U, long long *h_out, float *Jp_out, float *Jd_out);
+
+/* The batch: device pointers on the caller's stream, in the layout of 2c. */
+
+/* d_GQ [B][N*M] (16-byte aligned) <- Gp Qp_inv per problem (convertToDual's
+ * temporary, :491-492), in a layout private to the library (it belongs to
+ * the batch as a whole: not sliceable per problem).  Valid until Gp or Qp_inv
+ * change.  Synchronous; uses pqp_batch_convert_to_dual's workspace. */
+int pqp_batch_relin_prepare(int B, int N, int M, const float *d_Gp, const float *d_Qp_inv, float *d_GQ, void *stream);
+/* Fd [B][N] and Md [B] from new Fp [B][M], Mp [B], Kp [B][N]: ONE launch on
+ * `stream`, asynchronous, no allocation, no workspace lock, no
+ * synchronisation.  Bit-identical to pqp_batch_convert_to_dual's Fd, Md. */
+int pqp_batch_relinearize(int B, int N, int M, const float *d_GQ, const float *d_Qp_inv, const float *d_Kp,
+                          const float *d_Fp, const float *d_Mp, float *d_Fd, float *d_Md, void *stream);
+/* pqp_batch_solve_prepared started from d_Y0 [B][N] (it may be d_Y itself;
+ * NULL: cold, identical to pqp_batch_solve_prepared).  Every batched path
+ * (0, 1, 2 with both kernels, 3) honours it. */
+int pqp_batch_solve_from(int B, int N, int M, const float *d_Qd, const float *d_QdT, const float *d_theta,
+                         const int *d_sym, const float *d_GpT, const float *d_QinvT, const float *d_Fd,
+                         const float *d_Md, const float *d_Qp, const float *d_Qp_inv, const float *d_Fp,
+                         const float *d_Mp, const float *d_Gp, const float *d_Kp, int mode, long long num_iter,
+                         long long max_updates, float *d_Y, float *d_U, long long *d_h, int *d_status,
+                         const float *d_Y0, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

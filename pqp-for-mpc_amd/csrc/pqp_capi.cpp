@@ -19,6 +19,7 @@
 
 #include "pqp_internal.h"
 #include "pqp_launch.h"
+#include "pqp_relin.h"
 
 namespace pqp {
 
@@ -379,6 +380,7 @@ struct pqp_problem {
         struct Converge {  // converge mode as one persistent pipelined launch (pqp_converge.hip)
             pqp::DevBuf A1, A2, A3, rings, words;
         } conv;
+        pqp::DevBuf GQ;  // Gp Qp_inv in k_relin_pack's layout (pqp_problem_update_linear)
     } d;
 
     // handle-lifetime state: survives new data going into the handle
@@ -387,6 +389,8 @@ struct pqp_problem {
     bool own_stream = false;
     std::mutex mu;
     pqp::DevBuf Y, U, state;
+    pqp::DevBuf Y0;         // the iterate a warm solve starts from (a path that falls back starts from it again)
+    bool has_last = false;  // P.Y holds the final iterate of a solve of the current problem (PQP_START_LAST)
     pqp::PinnedBuf hout;  // mapped output of the one-launch tiny solves (kTinyOut* layout)
     pqp::PinnedBuf hin;   // staging of small problems' inputs
     pqp::PinnedBuf hio;   // staging of Y (N floats) then U (M floats)
@@ -438,6 +442,7 @@ int problem_finish(pqp_problem& P, hipStream_t s) {
     const int N = P.N, M = P.M;
     P.small = solve_small_lds_bytes(N, M) <= kLdsBudget;
     PQP_TRY(P.Y.floats(N));
+    PQP_TRY(P.Y0.floats(N));
     PQP_TRY(P.U.floats(M));
     // the state, then the int error word a one-launch tiny solve stores behind it (kTinyDevErr)
     PQP_TRY(P.state.alloc(sizeof(SolveState) + 16));
@@ -476,6 +481,7 @@ int problem_upload(pqp_problem& P, const float* qd, const float* fd, const float
     }
     P.N = N;
     P.M = M;
+    P.has_last = false;
     const size_t nn = (size_t)N * N, mm = (size_t)M * M, nm = (size_t)N * M;
     const size_t total = nn + N + 1 + 2 * mm + M + 1 + nm + N;
     // small problems: every input through one pinned staging buffer, so the
@@ -649,18 +655,26 @@ void report(const SolveState& st, SolveOut& out) {
     }
 }
 
+// The iterate a solve starts from, into P.Y: initMat(Y, 1000) (:710), or for a
+// warm solve y0 -- the handle's own P.Y0, which no path writes, so a path that
+// falls back to another starts from it again.
+hipError_t start_iterate(pqp_problem& P, const float* y0, hipStream_t s) {
+    if (!y0) return launch_fill(P.Y.f(), 1000.0f, P.N, s);
+    return hipMemcpyAsync(P.Y.p, y0, sizeof(float) * P.N, hipMemcpyDeviceToDevice, s);
+}
+
 // Fixed mode of a problem with N <= persist_max_n(): every update in ONE
 // persistent launch (pqp_persist.hip), launches of at most kPersistChunk
 // updates chained through P.Y.
 constexpr long long kPersistChunk = 1 << 16;
-int problem_run_fixed_persist(pqp_problem& P, long long updates, SolveOut& out, hipStream_t s) {
+int problem_run_fixed_persist(pqp_problem& P, long long updates, const float* y0, SolveOut& out, hipStream_t s) {
     const int N = P.N;
     PQP_TRY(ensure_persist_split(P, s));
     auto& ps = P.d.persist;
     float* Yb = P.d.Yb.f();
     auto* gran = static_cast<unsigned long long*>(ps.gran.p);
     int* err = static_cast<int*>(ps.err.p);
-    PQP_HIP(launch_fill(P.Y.f(), 1000.0f, N, s));  // initMat(Y, 1000) :710
+    PQP_HIP(start_iterate(P, y0, s));
     std::lock_guard<std::mutex> one_at_a_time(persist_lock());
     for (long long done = 0; done < updates;) {
         const long long n = std::min(kPersistChunk, updates - done);
@@ -689,14 +703,14 @@ int problem_run_fixed_persist(pqp_problem& P, long long updates, SolveOut& out, 
 // overhead would otherwise exceed the kernel itself): a chunk of kFixedChunk
 // updates replayed as often as needed, then a graph of the remainder.
 constexpr long long kFixedChunk = 256;  // even: a chunk starts and ends with the iterate in P.Y
-int problem_run_fixed_split(pqp_problem& P, long long num_iter, SolveOut& out, hipStream_t s) {
+int problem_run_fixed_split(pqp_problem& P, long long num_iter, const float* y0, SolveOut& out, hipStream_t s) {
     const int N = P.N;
     const long long updates = num_iter > 1 ? num_iter - 1 : 0;  // while(h < NUM_ITER)
     // one persistent launch when its workgroups can all be resident; if one of
     // its waits still expires (CUs held by other work), the solve restarts on
-    // the graph-replayed relay below (fixed mode restarts from Y = 1000)
+    // the graph-replayed relay below (from Y = 1000 again, or a warm solve's y0)
     if (!g_tune.persist_off && N <= persist_max_n() && split_persist_fits(N)) {
-        const int rc = problem_run_fixed_persist(P, updates, out, s);
+        const int rc = problem_run_fixed_persist(P, updates, y0, out, s);
         if (rc != kPersistStalled) return rc;
         ++g_persist_fallbacks;
     }
@@ -721,7 +735,7 @@ int problem_run_fixed_split(pqp_problem& P, long long num_iter, SolveOut& out, h
         PQP_TRY(capture_updates(P, rem, R.rem, s));
         R.graph_updates = rem;
     }
-    PQP_HIP(launch_fill(P.Y.f(), 1000.0f, N, s));  // initMat(Y, 1000) :710
+    PQP_HIP(start_iterate(P, y0, s));
     for (long long c = 0; c < full; ++c) PQP_HIP(hipGraphLaunch(R.chunk.exec, s));
     if (rem > 0) PQP_HIP(hipGraphLaunch(R.rem.exec, s));
     int herr = 0;
@@ -752,7 +766,8 @@ bool converge_persist_fits(int N, int M) {
 // (pqp_converge.hip): the update and the stages of terminate() run as
 // concurrent roles, terminate(Y_u) beside the update to Y_{u+1}.  Launches
 // decide at most g_tune.converge_chunk iterates each and are chained through P.Y.
-int problem_run_converge_persist(pqp_problem& P, long long max_updates, SolveOut& out, hipStream_t s) {
+int problem_run_converge_persist(pqp_problem& P, long long max_updates, const float* y0, SolveOut& out,
+                                 hipStream_t s) {
     const int N = P.N, M = P.M;
     PQP_TRY(ensure_persist_split(P, s));
     auto& C = P.d.conv;
@@ -775,7 +790,7 @@ int problem_run_converge_persist(pqp_problem& P, long long max_updates, SolveOut
     st.status = kStatusContinue;
     SolveState* dst = static_cast<SolveState*>(P.state.p);
     PQP_HIP(hipMemcpyAsync(dst, &st, sizeof st, hipMemcpyHostToDevice, s));
-    PQP_HIP(launch_fill(P.Y.f(), 1000.0f, N, s));  // initMat(Y, 1000) :710
+    PQP_HIP(start_iterate(P, y0, s));  // the launch's y_{u0}, u0 = 0: the entry a chunked relaunch takes
     char* words = static_cast<char*>(C.words.p);
     float* hio = P.hio.f();
     ConvergeLaunch L{};
@@ -833,12 +848,13 @@ int problem_run_converge_persist(pqp_problem& P, long long max_updates, SolveOut
 // Continue; launches after that point return at once.
 constexpr int kWideChunk = 16;      // even: each replay starts and ends with the iterate in P.Y
 constexpr int kWideFirstChunk = 2;  // the first replay of a solve
-int problem_run_wide(pqp_problem& P, long long max_updates, SolveOut& out, hipStream_t s, bool try_persist = true) {
+int problem_run_wide(pqp_problem& P, long long max_updates, const float* y0, SolveOut& out, hipStream_t s,
+                     bool try_persist = true) {
     const int N = P.N, M = P.M;
     if (try_persist && converge_persist_fits(N, M)) {
-        const int rc = problem_run_converge_persist(P, max_updates, out, s);
+        const int rc = problem_run_converge_persist(P, max_updates, y0, out, s);
         if (rc != kPersistStalled) return rc;
-        ++g_persist_fallbacks;  // converge mode restarts from Y = 1000 on the graph chain
+        ++g_persist_fallbacks;  // converge mode restarts (Y = 1000, or y0) on the graph chain
     }
     const int lw = pick_lw(N);
     PQP_TRY(ensure_split(P, lw, s));
@@ -914,6 +930,7 @@ int problem_run_wide(pqp_problem& P, long long max_updates, SolveOut& out, hipSt
         W.key = key;
     }
     PQP_HIP(launch_wide_init(dst, flag, cap, max_updates, P.Y.f(), N, s));
+    if (y0) PQP_HIP(start_iterate(P, y0, s));  // over the 1000s the init wrote
     SolveState& st = *P.hst.as<SolveState>();
     for (int launch = 0;; ++launch) {
         const GraphExec& g = launch < 2 ? W.first : (launch == 2 ? W.g4 : (launch == 3 ? W.g8 : W.full));
@@ -961,8 +978,8 @@ SolveArgs solve_args(const pqp_problem& P, int mode, long long num_iter, long lo
 // k_fixed_one / k_solve_quintet): the kernel starts from h = 1 itself (no state
 // upload) and writes Y, U, the state and its error word to pinned host memory,
 // so a solve is one launch and one synchronisation, no copy kernels.
-int problem_run_tiny(pqp_problem& P, int mode, long long num_iter, long long max_updates, SolveOut& out,
-                     hipStream_t s) {
+int problem_run_tiny(pqp_problem& P, int mode, long long num_iter, long long max_updates, const float* y0,
+                     SolveOut& out, hipStream_t s) {
     const int N = P.N, M = P.M;
     if (!P.hout.p) {
         // fine-grained (coherent) host memory: the kernel's stores reach it
@@ -977,6 +994,15 @@ int problem_run_tiny(pqp_problem& P, int mode, long long num_iter, long long max
     // the resume tests
     a.chunk = g_tune.tiny_chunk > 0 ? g_tune.tiny_chunk : updates_per_launch(N, M, 1 << 26, 1024);
     a.fresh = 1;
+    if (y0) {  // a warm start enters as a chunked relaunch does: the device state (h = 1) and its iterate
+        SolveState& st = *P.hst.as<SolveState>();
+        st = SolveState{};
+        st.h = 1;
+        st.resume = 1;
+        PQP_HIP(hipMemcpyAsync(P.state.p, &st, sizeof st, hipMemcpyHostToDevice, s));
+        PQP_HIP(start_iterate(P, y0, s));
+        a.fresh = 0;
+    }
     a.hout = P.hout.dev;
     a.tiny_flags = (g_tune.tiny_dense ? kTinyDense : 0) | (g_tune.tiny_stall ? kTinyStall : 0);
     a.trace = g_tune.tiny_trace;  // k_solve_quintet timing (bundled size only): 4 words per wave
@@ -1021,11 +1047,13 @@ int problem_run_tiny(pqp_problem& P, int mode, long long num_iter, long long max
 // solver (k_solve_tiny / _small / _single) run until it reports Done/Capped.
 // Each launch is bounded (chunk updates) so no launch runs unbounded.
 // `resume` = start from P.Y instead of Y = 1000 (used by the terminate()
-// drop-in, mode 2).
+// drop-in, mode 2).  `y0` (device, not P.Y) = a warm start: the solve takes
+// the path a cold one takes and starts from y0 instead of Y = 1000.
 int problem_run(pqp_problem& P, int mode, long long num_iter, long long max_updates, bool resume, SolveOut& out,
-                hipStream_t s) {
+                hipStream_t s, const float* y0 = nullptr) {
     const int N = P.N, M = P.M;
-    if (mode == kModeFixed && !P.small && !g_tune.force_single && !resume) return problem_run_fixed_split(P, num_iter, out, s);
+    if (mode == kModeFixed && !P.small && !g_tune.force_single && !resume)
+        return problem_run_fixed_split(P, num_iter, y0, out, s);
     if (mode == kModeConverge && !g_tune.force_single && !resume) {
         // the one-wave solver stays fastest for N, M <= 32 (0.65 us per iteration
         // at 32/16 against 2.3 on the persistent launch); from n_dual 48 up the
@@ -1033,23 +1061,24 @@ int problem_run(pqp_problem& P, int mode, long long num_iter, long long max_upda
         const bool tiny = N <= 32 && M <= 32 && !g_tune.force_small;
         const bool wide_ok = N >= g_tune.wide_min_n && (!P.small || g_tune.wide_min_n <= 0);
         if (!tiny && converge_persist_fits(N, M)) {
-            const int rc = problem_run_converge_persist(P, max_updates, out, s);
+            const int rc = problem_run_converge_persist(P, max_updates, y0, out, s);
             if (rc != kPersistStalled) return rc;
-            ++g_persist_fallbacks;  // the solve restarts from Y = 1000 below
-            if (wide_ok) return problem_run_wide(P, max_updates, out, s, false);
+            ++g_persist_fallbacks;  // the solve restarts (Y = 1000, or y0) below
+            if (wide_ok) return problem_run_wide(P, max_updates, y0, out, s, false);
         } else if (wide_ok) {
-            return problem_run_wide(P, max_updates, out, s);
+            return problem_run_wide(P, max_updates, y0, out, s);
         }
     }
     if (!resume && !g_tune.tiny_old && N <= 32 && M <= 32 && !g_tune.force_small && !g_tune.force_single &&
         (mode == kModeFixed || (mode == kModeConverge && N + M < 64)))
-        return problem_run_tiny(P, mode, num_iter, max_updates, out, s);
+        return problem_run_tiny(P, mode, num_iter, max_updates, y0, out, s);
     if (!P.small) PQP_TRY(ensure_single(P, s));
     SolveState& st = *P.hst.as<SolveState>();
     st = SolveState{};
     st.h = 1;
-    st.resume = resume ? 1 : 0;
+    st.resume = resume || y0 ? 1 : 0;
     PQP_HIP(hipMemcpyAsync(P.state.p, &st, sizeof st, hipMemcpyHostToDevice, s));
+    if (y0) PQP_HIP(start_iterate(P, y0, s));
     SolveArgs a = solve_args(P, mode, num_iter, max_updates);
     a.QdT = P.d.QdT.f();
     a.theta = P.d.theta.f();
@@ -1094,7 +1123,7 @@ using namespace pqp;
 
 extern "C" {
 
-int pqp_version(void) { return 106; }  // ABI revision: INTEGRATION.md section 6
+int pqp_version(void) { return 107; }  // ABI revision: INTEGRATION.md section 6
 
 // ---------------------------------------------------------------------------
 // 2a. status-returning host API
@@ -1145,16 +1174,40 @@ int pqp_problem_device(const pqp_problem* P) { return P ? P->dev : set_error(PQP
 
 int pqp_problem_solve(pqp_problem* P, int mode, long long num_iter, long long max_updates, float* Y, float* U,
                       long long* h_out, float* Jp_out, float* Jd_out) {
+    return pqp_problem_solve_from(P, PQP_START_COLD, nullptr, mode, num_iter, max_updates, Y, U, h_out, Jp_out,
+                                  Jd_out);
+}
+
+int pqp_problem_solve_from(pqp_problem* P, int start, const float* Y0, int mode, long long num_iter,
+                           long long max_updates, float* Y, float* U, long long* h_out, float* Jp_out,
+                           float* Jd_out) {
     if (!P || !Y) return set_error(PQP_ERR_ARG, "pqp_problem_solve: null handle or Y");
     if (mode != PQP_MODE_CONVERGE && mode != PQP_MODE_FIXED)
         return set_error(PQP_ERR_ARG, "pqp_problem_solve: unknown mode %d", mode);
+    if (start != PQP_START_COLD && start != PQP_START_HOST && start != PQP_START_LAST)
+        return set_error(PQP_ERR_ARG, "pqp_problem_solve_from: unknown start %d", start);
+    if (start == PQP_START_HOST && !Y0) return set_error(PQP_ERR_ARG, "pqp_problem_solve_from: PQP_START_HOST needs Y0");
     std::lock_guard<std::mutex> lk(P->mu);
+    if (start == PQP_START_LAST && !P->has_last)
+        return set_error(PQP_ERR_ARG, "pqp_problem_solve_from: PQP_START_LAST before the handle's first solve");
     DeviceGuard on(P->dev);
     PQP_TRY(ensure_device());
     hipStream_t s = P->stream;
+    // the starting iterate in a buffer of its own: the paths write P.Y
+    const float* y0 = nullptr;
+    if (start == PQP_START_HOST) {
+        std::memcpy(P->hio.p, Y0, sizeof(float) * P->N);  // through the pinned staging buffer
+        PQP_HIP(hipMemcpyAsync(P->Y0.p, P->hio.p, sizeof(float) * P->N, hipMemcpyHostToDevice, s));
+        y0 = P->Y0.f();
+    } else if (start == PQP_START_LAST) {
+        PQP_HIP(hipMemcpyAsync(P->Y0.p, P->Y.p, sizeof(float) * P->N, hipMemcpyDeviceToDevice, s));
+        y0 = P->Y0.f();
+    }
+    P->has_last = false;  // until this solve has left its final iterate in P.Y
     SolveOut o;
     PQP_TRY(problem_run(*P, mode == PQP_MODE_CONVERGE ? kModeConverge : kModeFixed, num_iter, max_updates, false, o,
-                        s));
+                        s, y0));
+    P->has_last = true;
     const bool want_u = U && mode == PQP_MODE_CONVERGE;
     float* hio = P->hio.f();
     if (!o.staged) {  // through the pinned staging buffer: one sync, no pageable DMA
@@ -1181,6 +1234,57 @@ int pqp_problem_destroy(pqp_problem* P) {
     }
     DeviceGuard on(P->dev);
     delete P;
+    return PQP_OK;
+}
+
+// Gp Qp_inv (convertToDual's temporary, PQP_CPU.c:491-492) in k_relin_pack's
+// layout, built on the first pqp_problem_update_linear of a problem.
+static int ensure_gq(pqp_problem& P, hipStream_t s) {
+    if (P.d.GQ.p) return PQP_OK;
+    const int N = P.N, M = P.M;
+    DevBuf rowmajor, packed;
+    PQP_TRY(rowmajor.floats((size_t)N * M));
+    PQP_TRY(packed.floats((size_t)N * M));
+    PQP_TRY(dev_matmul(rowmajor.f(), P.Gp.f(), 0, P.Qinv.f(), 0, N, M, M, s));  // Gp_Qp_inv :492
+    PQP_HIP(launch_relin_pack(1, N, M, rowmajor.f(), packed.f(), s));
+    PQP_HIP(hipStreamSynchronize(s));  // before the row-major copy is freed
+    P.d.GQ = std::move(packed);
+    return PQP_OK;
+}
+
+int pqp_problem_update_linear(pqp_problem* P, const float* Fp, const float* Mp, const float* Kp) {
+    if (!P || !Fp || !Mp) return set_error(PQP_ERR_ARG, "pqp_problem_update_linear: null handle, Fp or Mp");
+    std::lock_guard<std::mutex> lk(P->mu);
+    DeviceGuard on(P->dev);
+    PQP_TRY(ensure_device());
+    hipStream_t s = P->stream;
+    const int N = P->N, M = P->M;
+    PQP_TRY(ensure_gq(*P, s));
+    // in place: buffers of the same size keep their addresses (the captured graphs hold them)
+    PQP_TRY(upload(P->Fp, Fp, M, s));
+    PQP_TRY(upload(P->Mp, Mp, 1, s));
+    if (Kp) PQP_TRY(upload(P->Kp, Kp, N, s));
+    PQP_HIP(launch_relinearize(1, N, M, P->d.GQ.f(), P->Qinv.f(), P->Kp.f(), P->Fp.f(), P->Mp.f(), P->Fd.f(),
+                               P->Md.f(), s));
+    // what the solve paths derived from Fd, where it lives: the 32-lane
+    // layout's {Fdn, Fdp} (persistent launches) and the relay block's, which
+    // in the lean layout are the first two words of each row's aux
+    RelayBlock& rb = P->d.relay.block;
+    PQP_HIP(launch_relin_refresh(P->Fd.f(), N, P->d.persist.fdpn.f(), rb.lean ? nullptr : rb.fdpn.f(),
+                                 rb.lean ? rb.fdpn.f() : nullptr, s));
+    PQP_HIP(hipStreamSynchronize(s));
+    return PQP_OK;
+}
+
+int pqp_problem_get_dual(pqp_problem* P, float* Fd, float* Md) {
+    if (!P) return set_error(PQP_ERR_ARG, "pqp_problem_get_dual: null handle");
+    std::lock_guard<std::mutex> lk(P->mu);
+    DeviceGuard on(P->dev);
+    PQP_TRY(ensure_device());
+    hipStream_t s = P->stream;
+    if (Fd) PQP_TRY(download(Fd, P->Fd.p, P->N, s));
+    if (Md) PQP_TRY(download(Md, P->Md.p, 1, s));
+    PQP_HIP(hipStreamSynchronize(s));
     return PQP_OK;
 }
 
@@ -1556,6 +1660,38 @@ int pqp_batch_convert_to_dual(int B, int N, int M, const float* d_Qp_inv, const 
     return PQP_OK;
 }
 
+int pqp_batch_relin_prepare(int B, int N, int M, const float* d_Gp, const float* d_Qp_inv, float* d_GQ, void* stream) {
+    if (B <= 0 || N <= 0 || M <= 0 || !d_Gp || !d_Qp_inv || !d_GQ || (long long)B * N > 0x7fffffffLL)
+        return set_error(PQP_ERR_ARG, "pqp_batch_relin_prepare: bad arguments");
+    if (reinterpret_cast<uintptr_t>(d_GQ) & 15)
+        return set_error(PQP_ERR_ARG, "pqp_batch_relin_prepare: d_GQ must be 16-byte aligned");
+    PQP_TRY(ensure_device());
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const long long nm = (long long)N * M, mm = (long long)M * M;
+    // the row-major product in the device's setup workspace (held until the
+    // stream has synchronised), then its packets into d_GQ
+    SetupWorkspace wsp;
+    float* ws = nullptr;
+    PQP_TRY(wsp.acquire((size_t)B * nm, &ws));
+    PQP_HIP(launch_matmul_seq_b(B, ws, d_Gp, 0, d_Qp_inv, 0, N, M, M, nm, mm, nm, s));  // Gp_Qp_inv :492
+    PQP_HIP(launch_relin_pack(B, N, M, ws, d_GQ, s));
+    PQP_HIP(hipStreamSynchronize(s));
+    return PQP_OK;
+}
+
+int pqp_batch_relinearize(int B, int N, int M, const float* d_GQ, const float* d_Qp_inv, const float* d_Kp,
+                          const float* d_Fp, const float* d_Mp, float* d_Fd, float* d_Md, void* stream) {
+    if (B <= 0 || N <= 0 || M <= 0 || !d_GQ || !d_Qp_inv || !d_Kp || !d_Fp || !d_Mp || !d_Fd || !d_Md ||
+        (long long)B * N > 0x7fffffffLL)
+        return set_error(PQP_ERR_ARG, "pqp_batch_relinearize: bad arguments");
+    if (reinterpret_cast<uintptr_t>(d_GQ) & 15)
+        return set_error(PQP_ERR_ARG, "pqp_batch_relinearize: d_GQ must be 16-byte aligned");
+    PQP_TRY(ensure_device());
+    PQP_HIP(launch_relinearize(B, N, M, d_GQ, d_Qp_inv, d_Kp, d_Fp, d_Mp, d_Fd, d_Md,
+                               static_cast<hipStream_t>(stream)));
+    return PQP_OK;
+}
+
 int pqp_batch_compute_fp(int B, int m, int nd, int ns, const float* d_Fp1, const float* d_Fp2, const float* d_Fp3,
                          const float* d_D, const float* d_x, float* d_Fp, void* stream) {
     if (B <= 0 || m <= 0 || nd <= 0 || ns <= 0 || !d_Fp1 || !d_Fp2 || !d_Fp3 || !d_D || !d_x || !d_Fp)
@@ -1665,6 +1801,17 @@ int pqp_batch_solve_prepared(int B, int N, int M, const float* d_Qd, const float
                              const float* d_Mp, const float* d_Gp, const float* d_Kp, int mode, long long num_iter,
                              long long max_updates, float* d_Y, float* d_U, long long* d_h, int* d_status,
                              void* stream) {
+    return pqp_batch_solve_from(B, N, M, d_Qd, d_QdT, d_theta, d_sym, d_GpT, d_QinvT, d_Fd, d_Md, d_Qp, d_Qp_inv, d_Fp,
+                                d_Mp, d_Gp, d_Kp, mode, num_iter, max_updates, d_Y, d_U, d_h, d_status, nullptr,
+                                stream);
+}
+
+int pqp_batch_solve_from(int B, int N, int M, const float* d_Qd, const float* d_QdT, const float* d_theta,
+                         const int* d_sym, const float* d_GpT, const float* d_QinvT, const float* d_Fd,
+                         const float* d_Md, const float* d_Qp, const float* d_Qp_inv, const float* d_Fp,
+                         const float* d_Mp, const float* d_Gp, const float* d_Kp, int mode, long long num_iter,
+                         long long max_updates, float* d_Y, float* d_U, long long* d_h, int* d_status,
+                         const float* d_Y0, void* stream) {
     if (B <= 0 || N <= 0 || M <= 0 || !d_Qd || !d_Fd || !d_Y)
         return set_error(PQP_ERR_ARG, "pqp_batch_solve: bad arguments");
     if (mode != PQP_MODE_CONVERGE && mode != PQP_MODE_FIXED)
@@ -1688,7 +1835,10 @@ int pqp_batch_solve_prepared(int B, int N, int M, const float* d_Qd, const float
     }
     PQP_TRY(state.alloc(sizeof(SolveState) * (size_t)B));
     PQP_TRY(pending.alloc(sizeof(int)));
-    PQP_HIP(launch_state_init(B, static_cast<SolveState*>(state.p), s));
+    // a warm start enters as a chunked relaunch does: h = 1 with its iterate in d_Y
+    PQP_HIP((d_Y0 ? launch_state_init_warm : launch_state_init)(B, static_cast<SolveState*>(state.p), s));
+    if (d_Y0 && d_Y0 != d_Y)
+        PQP_HIP(hipMemcpyAsync(d_Y, d_Y0, sizeof(float) * (size_t)B * N, hipMemcpyDeviceToDevice, s));
     SolveArgs a{};
     a.QdT = path == 2 ? (d_QdT ? d_QdT : d_Qd) : nullptr;
     a.Qd = d_Qd;

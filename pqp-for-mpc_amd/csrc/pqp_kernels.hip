@@ -5678,3 +5678,7 @@ hipError_t launch_extract_state(int B, const SolveState* st, long long* h, int* 
 }
 
 }  // namespace pqp
+
+// The relinearization kernels (k_relinearize and its companions) live in a file of their own and
+// are compiled into this object, so that the list of kernel objects every link line names stays as it is.
+#include "pqp_relin.hip"

@@ -13,7 +13,7 @@ Layers
     Gauss_Jordan, computeFp, computeMp
   * status API: solve_dual, update, read_example, run_example
   * batched device API (torch tensors as device memory): :class:`Batch`,
-    :class:`ProblemBatch`, :func:`mpc_batch`, :func:`horizon_batch`
+    :class:`ProblemBatch`, :func:`mpc_batch`, :func:`mpc_restate`, :func:`horizon_batch`
   * row blocks of one large problem (row-sharded solve): :class:`RowBlock`
     (driver in :mod:`pqp_amd.rowshard`)
 """
@@ -34,6 +34,7 @@ PQP_OK = 0
 PQP_ERR_ARG, PQP_ERR_HIP, PQP_ERR_ALLOC, PQP_ERR_IO, PQP_ERR_NOT_CONVERGED, PQP_ERR_NO_DEVICE = -1, -2, -3, -4, -5, -6
 PQP_ERR_NEEDS_QDT = -7
 MODE_CONVERGE, MODE_FIXED = 0, 1
+START_COLD, START_HOST, START_LAST = 0, 1, 2
 
 # The reference's compile-time problem dimensions (PQP_CPU.c:13-17).
 P_HORIZON, N_STATE, N_INPUT, N_OUTPUT, N_DIS = 1, 29, 7, 7, 1
@@ -90,6 +91,14 @@ SIGNATURES = {
     "pqp_batch_prepare": (C.c_int, [C.c_int] * 3 + [_vp] * 8 + [C.POINTER(C.c_int), _vp]),
     "pqp_batch_solve_prepared": (C.c_int, [C.c_int] * 3 + [_vp] * 14 + [C.c_int, C.c_longlong, C.c_longlong]
                                  + [_vp] * 4 + [_vp]),
+    "pqp_problem_update_linear": (C.c_int, [_vp, _fp, _fp, _fp]),
+    "pqp_problem_get_dual": (C.c_int, [_vp, _fp, _fp]),
+    "pqp_problem_solve_from": (C.c_int, [_vp, C.c_int, _fp, C.c_int, C.c_longlong, C.c_longlong, _fp, _fp,
+                                         C.POINTER(C.c_longlong), _fp, _fp]),
+    "pqp_batch_relin_prepare": (C.c_int, [C.c_int] * 3 + [_vp] * 3 + [_vp]),
+    "pqp_batch_relinearize": (C.c_int, [C.c_int] * 3 + [_vp] * 7 + [_vp]),
+    "pqp_batch_solve_from": (C.c_int, [C.c_int] * 3 + [_vp] * 14 + [C.c_int, C.c_longlong, C.c_longlong]
+                             + [_vp] * 4 + [_vp, _vp]),
     "pqp_rowblock_create": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, C.POINTER(C.c_void_p)]),
     "pqp_rowblock_update": (C.c_int, [_vp, _vp, _vp, _vp]),
     "pqp_rowblock_check": (C.c_int, [_vp, _vp]),
@@ -360,13 +369,49 @@ class Problem:
     def device(self) -> int:
         return int(lib().pqp_problem_device(self._h))
 
-    def solve(self, mode: int = MODE_CONVERGE, num_iter: int = 1000, max_updates: int = 0) -> dict:
+    def solve(self, mode: int = MODE_CONVERGE, num_iter: int = 1000, max_updates: int = 0, y0=None) -> dict:
+        """Solve from Y = 1000 (y0=None), from the array y0 (N floats), or, with
+        y0="last", from the final iterate of this handle's previous solve
+        (device-resident: no upload).  A warm solve is the reference's loop with
+        initMat(Y, 1000) replaced by Y = y0 -- h starts at 1 again -- and takes
+        the solver path a cold solve takes."""
         with self._lock:
-            rc = self._solve(self._h, mode, num_iter, max_updates, *self._args)
+            if y0 is None:
+                rc = self._solve(self._h, mode, num_iter, max_updates, *self._args)
+            elif isinstance(y0, str):
+                if y0 != "last":
+                    raise ValueError('y0 must be an array, "last" or None')
+                rc = lib().pqp_problem_solve_from(self._h, START_LAST, None, mode, num_iter, max_updates, *self._args)
+            else:
+                y = _f32(y0).reshape(-1)
+                if y.size != self.N:
+                    raise ValueError(f"y0 must have {self.N} entries")
+                rc = lib().pqp_problem_solve_from(self._h, START_HOST, _buf(y), mode, num_iter, max_updates,
+                                                  *self._args)
             if rc not in (PQP_OK, PQP_ERR_NOT_CONVERGED):
                 _check(rc)
             return dict(h=int(self._hv.value), Y=self._Y.copy(), U=self._U.copy(), Jp=float(self._jp[0]),
                         Jd=float(self._jd[0]), converged=(rc == PQP_OK))
+
+    def update_linear(self, Fp, Mp, Kp=None):
+        """New linear terms for the resident problem (pqp_problem_update_linear):
+        Fd and Md are recomputed on the device as convertToDual would, and what
+        the solve paths derived from Fd is refreshed in place; Qd, Theta, the
+        packed matrices and the captured graphs are kept."""
+        fp, mp = _f32(Fp).reshape(-1), _f32(Mp).reshape(-1)
+        kp = None if Kp is None else _f32(Kp).reshape(-1)
+        if fp.size != self.M or mp.size != 1 or (kp is not None and kp.size != self.N):
+            raise ValueError("update_linear: Fp is M floats, Mp one, Kp N")
+        with self._lock:
+            _check(lib().pqp_problem_update_linear(self._h, _buf(fp), _buf(mp), None if kp is None else _buf(kp)))
+        return self
+
+    def dual(self):
+        """The handle's current (Fd, Md) (pqp_problem_get_dual)."""
+        Fd, Md = np.zeros(self.N, np.float32), np.zeros(1, np.float32)
+        with self._lock:
+            _check(lib().pqp_problem_get_dual(self._h, _buf(Fd), _buf(Md)))
+        return Fd, Md
 
     def close(self):
         if self._h:
@@ -590,6 +635,7 @@ class ProblemBatch:
         self.B, self.N, self.M = int(B), int(N), int(M)
         self.transposes = bool(transposes)  # prepare() keeps Gp', Qp_inv' for coalesced row walks (path 2)
         self._prep = None  # pqp_batch_prepare's per-problem data, until Qd / Gp / Qp_inv change
+        self._gq = None  # (key, Gp Qp_inv in the library's layout) of relinearize(), until Gp / Qp_inv change
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         f = dict(dtype=torch.float32, device=self.device)
         B, N, M = self.B, self.N, self.M
@@ -649,6 +695,7 @@ class ProblemBatch:
         writes to Qd, Gp or Qp_inv by itself (torch's version counters), so
         this is only needed after writes torch cannot see (e.g. from C)."""
         self._prep = None
+        self._gq = None
         return self
 
     def _source_key(self):
@@ -704,10 +751,48 @@ class ProblemBatch:
                                                                          self.PRIMAL + self.DUAL], self._s()))
         return self.invalidate()
 
-    def solve(self, mode: int = MODE_CONVERGE, num_iter: int = 1000, max_updates: int = 0, prepared: bool = True):
+    def relinearize(self):
+        """Fd and Md from the tensors' current Fp, Mp and Kp, in one
+        asynchronous launch (pqp_batch_relinearize) -- the step between two
+        solves of a receding-horizon loop, where only the linear terms move.
+        Gp Qp_inv is computed on the first call (pqp_batch_relin_prepare) and
+        kept until Gp or Qp_inv change.  Qd did not change, so what prepare()
+        derived from it stays."""
+        torch = self.torch
+        key = tuple((t.data_ptr(), t._version) for t in (self.Gp, self.Qp_inv))
+        if self._gq is None or self._gq[0] != key:
+            gq = torch.empty(self.B, self.N * self.M, dtype=torch.float32, device=self.device)
+            _check(lib().pqp_batch_relin_prepare(self.B, self.N, self.M, self._p(self.Gp), self._p(self.Qp_inv),
+                                                 self._p(gq), self._s()))
+            self._gq = (key, gq)
+        _check(lib().pqp_batch_relinearize(self.B, self.N, self.M, self._p(self._gq[1]), self._p(self.Qp_inv),
+                                           self._p(self.Kp), self._p(self.Fp), self._p(self.Mp), self._p(self.Fd),
+                                           self._p(self.Md), self._s()))
+        return self
+
+    def solve(self, mode: int = MODE_CONVERGE, num_iter: int = 1000, max_updates: int = 0, prepared: bool = True,
+              warm: bool = False, floor: float | None = None):
         """solveQuadraticDual for every problem; fills Y, U, h, status.  The
         per-problem setup is prepared on the first call and reused
-        (prepared=False: pqp_batch_solve, which redoes it every call)."""
+        (prepared=False: pqp_batch_solve, which redoes it every call).
+
+        warm=True starts every problem from its row of ``self.Y`` -- the
+        previous solve's result, or whatever the caller put there -- instead of
+        Y = 1000 (pqp_batch_solve_from): the reference's loop with
+        initMat(Y, 1000) replaced, h starting at 1 again.
+
+        floor: the start is ``self.Y.clamp_min(floor)``.  It exists because the
+        update is multiplicative, Y_next[i] = Y[i] * num_i / den_i: an entry
+        that reached exactly 0 stays 0 whatever the new problem wants of it.
+        The synthetic problems do this (Y* of seed 11 at (24, 8) has 12 exact
+        zeros, and a warm solve of a moved problem from it never converges);
+        the bundled plant's Y* has none (its smallest entry is 2.8e-28), but a
+        floor of 1e-3 there costs one update (h = 2 instead of 1)."""
+        if (warm or floor is not None) and not prepared:
+            raise ValueError("a warm solve runs on the prepared data (prepared=True)")
+        if floor is not None:
+            warm = True
+            self.Y.clamp_min_(float(floor))
         if not prepared:
             _check(lib().pqp_batch_solve(self.B, self.N, self.M, *[self._p(getattr(self, k)) for k in
                                                                   ("Qd", "Fd", "Md", "Qp", "Qp_inv", "Fp", "Mp",
@@ -719,12 +804,13 @@ class ProblemBatch:
             self.prepare()  # first solve, Qd / Gp / Qp_inv written, or a knob moved the size to another solver
         P = self._prep
         p = lambda k: self._p(P[k]) if P.get(k) is not None else None  # noqa: E731
-        _check(lib().pqp_batch_solve_prepared(self.B, self.N, self.M, self._p(self.Qd), p("QdT"), p("theta"), p("sym"),
-                                              p("GpT"), p("QinvT"),
-                                              *[self._p(getattr(self, k)) for k in
-                                                ("Fd", "Md", "Qp", "Qp_inv", "Fp", "Mp", "Gp", "Kp")],
-                                              mode, num_iter, max_updates, self._p(self.Y), self._p(self.U),
-                                              self._p(self.h), self._p(self.status), self._s()))
+        args = (self.B, self.N, self.M, self._p(self.Qd), p("QdT"), p("theta"), p("sym"), p("GpT"), p("QinvT"),
+                *[self._p(getattr(self, k)) for k in ("Fd", "Md", "Qp", "Qp_inv", "Fp", "Mp", "Gp", "Kp")],
+                mode, num_iter, max_updates, self._p(self.Y), self._p(self.U), self._p(self.h), self._p(self.status))
+        if warm:  # d_Y0 is d_Y itself: no copy
+            _check(lib().pqp_batch_solve_from(*args, self._p(self.Y), self._s()))
+        else:
+            _check(lib().pqp_batch_solve_prepared(*args, self._s()))
         return self
 
 
@@ -758,14 +844,49 @@ def mpc_batch(directory, states, device=None) -> ProblemBatch:
     D = T(np.tile(E["D"], (B, 1)))
     for k in ("Qp_inv", "Gp", "Kp"):
         getattr(pb, k).copy_(T(E[k]).reshape(1, -1).expand(B, -1))
+    _mpc_linear_terms(pb, E, plant, D, x)
+    pb.gauss_jordan().convert_to_dual()
+    pb._plant = (str(directory), E, plant, D)  # for mpc_restate
+    return pb
+
+
+def _mpc_linear_terms(pb, E, plant, D, x):
+    """pb.Fp, pb.Mp <- computeFp / computeMp of the plant at states x (device)."""
     p = ProblemBatch._p
     s = pb._s()
-    _check(lib().pqp_batch_compute_fp(B, E["M"], E["nd"], ns, p(plant["Fp1"]), p(plant["Fp2"]), p(plant["Fp3"]),
+    B = pb.B
+    _check(lib().pqp_batch_compute_fp(B, E["M"], E["nd"], E["ns"], p(plant["Fp1"]), p(plant["Fp2"]), p(plant["Fp3"]),
                                       p(D), p(x), p(pb.Fp), s))
-    _check(lib().pqp_batch_compute_mp(B, E["nd"], ns, *[p(plant[k]) for k in ("Mp1", "Mp2", "Mp3", "Mp4", "Mp5",
-                                                                                "Mp6")], p(D), p(x), p(pb.Mp), s))
-    pb.gauss_jordan().convert_to_dual()
-    return pb
+    _check(lib().pqp_batch_compute_mp(B, E["nd"], E["ns"], *[p(plant[k]) for k in ("Mp1", "Mp2", "Mp3", "Mp4", "Mp5",
+                                                                                     "Mp6")], p(D), p(x), p(pb.Mp), s))
+
+
+def mpc_restate(pb: ProblemBatch, directory, states) -> ProblemBatch:
+    """The closed-loop counterpart of mpc_batch: the same B problems at new
+    states.  Only Fp and Mp depend on the state (computeFp / computeMp), and
+    through them Fd and Md: both are recomputed in place
+    (pqp_batch_compute_fp / _mp, then ProblemBatch.relinearize), while Qd, Qp
+    and everything prepared from them stay.  Follow it with ``pb.solve()`` or,
+    to start from the previous step's Y, ``pb.solve(warm=True)``."""
+    import torch
+
+    cached = getattr(pb, "_plant", None)
+    if cached is not None and cached[0] == str(directory):
+        _, E, plant, D = cached
+    else:
+        E = read_example(directory)
+        if (E["N"], E["M"]) != (pb.N, pb.M):
+            raise ValueError("mpc_restate: the batch is not this plant's")
+        T = lambda a: torch.as_tensor(np.asarray(a, np.float32), device=pb.device).contiguous()  # noqa: E731
+        plant = {k: T(E[k]) for k in ("Fp1", "Fp2", "Fp3", "Mp1", "Mp2", "Mp3", "Mp4", "Mp5", "Mp6")}
+        D = T(np.tile(E["D"], (pb.B, 1)))
+        pb._plant = (str(directory), E, plant, D)
+    xs = states if torch.is_tensor(states) else np.ascontiguousarray(np.asarray(states, np.float32))
+    x = torch.as_tensor(xs, dtype=torch.float32, device=pb.device).reshape(pb.B, -1).contiguous()
+    if x.shape[1] != E["ns"]:
+        raise ValueError(f"states must be [{pb.B}, {E['ns']}]")
+    _mpc_linear_terms(pb, E, plant, D, x)  # synchronous: x may go out of scope after it
+    return pb.relinearize()
 
 
 def horizon_batch(directory, H: int, states, device=None) -> ProblemBatch:
