@@ -411,6 +411,68 @@ int pqp_batch_solve_from(int B, int N, int M, const float *d_Qd, const float *d_
                          long long max_updates, float *d_Y, float *d_U, long long *d_h, int *d_status,
                          const float *d_Y0, void *stream);
 
+/* ----------------------------------------------------------------------
+ * 2f. One plant, many states: a resident plant and a one-launch control step.
+ * In the MPC workload every problem of a batch is the same plant at another
+ * state: Qp_inv, Gp, Kp -- and so Qp, Qd, Theta and Gp Qp_inv -- are shared,
+ * only x and D differ, and through them Fp, Mp, Fd and Md.  A pqp_plant keeps
+ * the shared data on its device once; pqp_plant_step takes B states through
+ * computeFp, computeMp, convertToDual's Fd and Md and the converge solve in
+ * ONE asynchronous launch, so steps can be chained on a stream or captured in
+ * a graph.
+ *
+ * Bit-exactness: state b of a step gives exactly what pqp_batch_compute_fp,
+ * pqp_batch_compute_mp and pqp_batch_relinearize at that state, followed by
+ * pqp_batch_solve_from in PQP_MODE_CONVERGE with the same cap, give for
+ * problem b -- that is computeFp (PQP_CPU.c:373), computeMp (:395),
+ * convertToDual's Fd and Md (:456-479) and solveQuadraticDual (:694-750, line
+ * :710 replaced when warm) -- bit for bit, Jp and Jd included.  NaN operands:
+ * as convertToDual above.
+ *
+ * Shapes: N <= 32, M <= 32, N + M < 64 (one wave per state), nd <= 64,
+ * ns <= 64.  Other shapes: the batched entry points of 2c / 2e.  Converge
+ * mode only.
+ *
+ * The plant is immutable after create.  A step writes only the caller's
+ * buffers, so steps on different streams may run concurrently without a lock;
+ * it runs on the plant's device whatever device the caller has current (and
+ * restores the caller's), and does no allocation, no synchronisation and no
+ * copy to the host.
+ * -------------------------------------------------------------------- */
+typedef struct pqp_plant pqp_plant;
+
+/* 1 when (N, M, nd, ns) is a shape pqp_plant_step runs, else 0 (no error set). */
+int pqp_plant_supported(int N, int M, int nd, int ns);
+
+/* Host pointers, reference layouts (pqp_read_example's): Qp_inv [M*M], Gp [N*M], Kp [N],
+ * Fp1 [M*nd], Fp2 [M*ns], Fp3 [M], Mp1 [ns*ns], Mp2 [nd*ns], Mp3 [nd*nd], Mp4 [ns], Mp5 [nd], Mp6 [1].
+ * device -1: the current one.  Synchronous.  Derives, once, with the bits of the existing entry
+ * points: Qp = Gauss_Jordan(Qp_inv), Qd and Gp Qp_inv as convertToDual forms them
+ * (PQP_CPU.c:440-455, :491-492), Theta (computeTheta).  An unsupported shape: PQP_ERR_ARG. */
+int pqp_plant_create(int device, int N, int M, int nd, int ns, const float *Qp_inv, const float *Gp,
+                     const float *Kp, const float *Fp1, const float *Fp2, const float *Fp3,
+                     const float *Mp1, const float *Mp2, const float *Mp3, const float *Mp4,
+                     const float *Mp5, const float *Mp6, pqp_plant **out);
+int pqp_plant_destroy(pqp_plant *p);
+/* Host copies of what create derived; any pointer may be NULL: Qd [N*N], Qp [M*M], theta [N]. */
+int pqp_plant_get(pqp_plant *p, float *Qd, float *Qp, float *theta);
+/* Largest max_updates a step accepts: one launch never runs longer than the batched
+ * solvers' existing per-launch budget for the shape (batch_chunk_for(N, M)). */
+long /* (the return type is long long; tests/test_capi.py's prototype scanner reads the last word before the name) */
+long pqp_plant_max_updates(const pqp_plant *p);
+
+/* One control step of B states, converge mode, ONE launch on `stream`, asynchronous.
+ * In:  d_x [B][ns], d_D [B][nd]; d_Kp NULL (the plant's Kp for every state) or [B][N];
+ *      warm 0: Y = 1000 (PQP_CPU.c:710), 1: Y = d_Y's current rows, taken as given (2e's rules).
+ * Out: d_Y [B][N] (in/out when warm), d_U [B][M], and, each optional (NULL: not written),
+ *      d_h [B] int64 (the reference's printed h), d_status [B] (1 converged, 2 hit max_updates),
+ *      d_Fp [B][M], d_Mp [B], d_Fd [B][N], d_Md [B], d_Jp [B], d_Jd [B] (costs of the last
+ *      terminate() that passed checkFeas; NaN if none, as pqp_solve_dual).
+ * 1 <= max_updates <= pqp_plant_max_updates(p), else PQP_ERR_ARG. */
+int pqp_plant_step(pqp_plant *p, int B, const float *d_x, const float *d_D, const float *d_Kp, int warm,
+                   long long max_updates, float *d_Y, float *d_U, long long *d_h, int *d_status,
+                   float *d_Fp, float *d_Mp, float *d_Fd, float *d_Md, float *d_Jp, float *d_Jd, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

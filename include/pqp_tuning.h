@@ -109,6 +109,11 @@ extern "C" {
  *                          other multiples of 1024: k_batch_stream; else
  *                          k_batch_iterate), 1 k_batch_iterate, 2 k_batch_stream,
  *                          3 k_batch_resident without the register blocks
+ *   plant_grid [0]         pqp_plant_step: at most this many workgroups (0: every
+ *                          resident wave slot), so that a small batch walks the
+ *                          kernel's state loop (tests)
+ *   plant_pipe [0]         pqp_plant_step's iteration: 0 plain, 1 software-pipelined
+ *                          (k_solve_wave's two forms)
  *  Paths and failure tests:
  *   persist_off [0]        fixed mode of n_dual <= 1024 through the graph-replayed
  *                          relay instead of the persistent launch
@@ -139,7 +144,10 @@ int pqp_tune(const char *key, long long value, long long *old_value);
  *   converge_grid      in: *value = N << 32 | M; out: workgroups of the
  *                      persistent converge launch for (N, M) (0: not used)
  *   batch_chunk_for    in: *value = N << 32 | M; out: iterates per problem per
- *                      pqp_batch_solve launch (the batch_chunk knob if set) */
+ *                      pqp_batch_solve launch (the batch_chunk knob if set)
+ *   plant_slots        in: *value = N | M << 8 | nd << 16 | ns << 24 | pipe << 32;
+ *                      out: workgroups of pqp_plant_step resident at once on the
+ *                      current device (CUs x occupancy): its grid is min(B, that) */
 int pqp_tune_get(const char *key, long long *value);
 
 /* Record an on-device timeline (s_memrealtime / s_memtime marks) of the

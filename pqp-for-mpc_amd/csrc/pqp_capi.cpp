@@ -19,6 +19,7 @@
 
 #include "pqp_internal.h"
 #include "pqp_launch.h"
+#include "pqp_plant.h"
 #include "pqp_relin.h"
 
 namespace pqp {
@@ -407,6 +408,18 @@ struct pqp_rowblock {
     int N = 0, row0 = 0, rows = 0;
     int dev = -1;  // the device it was made on (its calls run there)
     pqp::RelayBlock relay;
+};
+
+// One plant resident on its device (pqp_plant_*): the primal data as given,
+// what create derived from them, and the pointers a step hands its launch.
+// Immutable after create; a step writes only the caller's buffers.
+struct pqp_plant {
+    int N = 0, M = 0, nd = 0, ns = 0;
+    int dev = -1;            // the device it was made on (its steps run there)
+    int slots[2] = {0, 0};   // workgroups resident at once: [0] the plain form, [1] the pipelined one
+    pqp::DevBuf Qinv, Gp, Kp, Qp, Qd, GQ, theta;
+    pqp::DevBuf Fp1, Fp2, Fp3, Mp1, Mp2, Mp3, Mp4, Mp5, Mp6;
+    pqp::PlantData data{};
 };
 
 namespace pqp {
@@ -1123,7 +1136,7 @@ using namespace pqp;
 
 extern "C" {
 
-int pqp_version(void) { return 107; }  // ABI revision: INTEGRATION.md section 6
+int pqp_version(void) { return 108; }  // ABI revision: INTEGRATION.md section 6
 
 // ---------------------------------------------------------------------------
 // 2a. status-returning host API
@@ -1917,6 +1930,125 @@ int pqp_batch_solve(int B, int N, int M, const float* d_Qd, const float* d_Fd, c
 }
 
 // ---------------------------------------------------------------------------
+// 2f. a resident plant and a one-launch control step
+// ---------------------------------------------------------------------------
+int pqp_plant_supported(int N, int M, int nd, int ns) { return plant_shape_ok(N, M, nd, ns) ? 1 : 0; }
+
+int pqp_plant_create(int device, int N, int M, int nd, int ns, const float* Qp_inv, const float* Gp, const float* Kp,
+                     const float* Fp1, const float* Fp2, const float* Fp3, const float* Mp1, const float* Mp2,
+                     const float* Mp3, const float* Mp4, const float* Mp5, const float* Mp6, pqp_plant** out) {
+    if (!out) return set_error(PQP_ERR_ARG, "pqp_plant_create: null handle pointer");
+    *out = nullptr;
+    if (!plant_shape_ok(N, M, nd, ns))
+        return set_error(PQP_ERR_ARG, "pqp_plant_create: (N=%d, M=%d, nd=%d, ns=%d) is not a shape pqp_plant_step runs "
+                                      "(N <= 32, M <= 32, N + M < 64, nd <= 64, ns <= 64): use ProblemBatch "
+                                      "(pqp_batch_*) for it", N, M, nd, ns);
+    if (!Qp_inv || !Gp || !Kp || !Fp1 || !Fp2 || !Fp3 || !Mp1 || !Mp2 || !Mp3 || !Mp4 || !Mp5 || !Mp6)
+        return set_error(PQP_ERR_ARG, "pqp_plant_create: null input");
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return set_error(PQP_ERR_NO_DEVICE, "libpqp: no HIP device visible");
+    if (device < 0 && hipGetDevice(&device) != hipSuccess)
+        return set_error(PQP_ERR_NO_DEVICE, "libpqp: cannot query the current device");
+    if (device >= n) return set_error(PQP_ERR_ARG, "pqp_plant_create: device %d of %d", device, n);
+    DeviceGuard on(device);
+    PQP_TRY(ensure_device());
+    hipStream_t s = lib_stream();
+    std::unique_ptr<pqp_plant> P(new pqp_plant());
+    P->N = N, P->M = M, P->nd = nd, P->ns = ns;
+    P->dev = device;
+    PQP_TRY(upload(P->Qinv, Qp_inv, (size_t)M * M, s));
+    PQP_TRY(upload(P->Gp, Gp, (size_t)N * M, s));
+    PQP_TRY(upload(P->Kp, Kp, N, s));
+    PQP_TRY(upload(P->Fp1, Fp1, (size_t)M * nd, s));
+    PQP_TRY(upload(P->Fp2, Fp2, (size_t)M * ns, s));
+    PQP_TRY(upload(P->Fp3, Fp3, M, s));
+    PQP_TRY(upload(P->Mp1, Mp1, (size_t)ns * ns, s));
+    PQP_TRY(upload(P->Mp2, Mp2, (size_t)nd * ns, s));
+    PQP_TRY(upload(P->Mp3, Mp3, (size_t)nd * nd, s));
+    PQP_TRY(upload(P->Mp4, Mp4, ns, s));
+    PQP_TRY(upload(P->Mp5, Mp5, nd, s));
+    PQP_TRY(upload(P->Mp6, Mp6, 1, s));
+    PQP_TRY(P->Qp.floats((size_t)M * M));
+    PQP_TRY(P->Qd.floats((size_t)N * N));
+    PQP_TRY(P->GQ.floats((size_t)N * M));
+    PQP_TRY(P->theta.floats(N));
+    // what every state shares, once, by the launchers the batched entry points use (B = 1)
+    DevBuf aug, fac;
+    PQP_TRY(aug.floats(gauss_jordan_aug_floats(M)));
+    PQP_TRY(fac.floats(M));
+    const long long nm = (long long)N * M, mm = (long long)M * M, nn = (long long)N * N;
+    PQP_HIP(launch_gauss_jordan_b(1, P->Qinv.f(), aug.f(), fac.f(), P->Qp.f(), M, s));                       // Qp :251
+    PQP_HIP(launch_matmul_seq_b(1, P->GQ.f(), P->Gp.f(), 0, P->Qinv.f(), 0, N, M, M, nm, mm, nm, s));      // Gp Qp_inv :492
+    PQP_HIP(launch_matmul_seq_b(1, P->Qd.f(), P->GQ.f(), 0, P->Gp.f(), 1, N, M, N, nm, nm, nn, s));        // Qd :440-455
+    PQP_HIP(launch_theta_rows(P->Qd.f(), N, N, N, P->theta.f(), s));                                       // Theta :503-519
+    for (int pipe = 0; pipe < 2; ++pipe) {
+        P->slots[pipe] = plant_resident_wgs(N, M, nd, ns, pipe != 0);
+        if (P->slots[pipe] <= 0) {
+            const hipError_t e = hipGetLastError();
+            return set_error(PQP_ERR_HIP, "pqp_plant_create: no occupancy for (N=%d, M=%d, nd=%d, ns=%d): %s", N, M, nd,
+                             ns, hipGetErrorString(e));
+        }
+    }
+    PQP_HIP(hipStreamSynchronize(s));  // the host arrays and the Gauss_Jordan scratch are free after it
+    PlantData& d = P->data;
+    d.N = N, d.M = M, d.nd = nd, d.ns = ns;
+    d.Qd = P->Qd.f(), d.Gp = P->Gp.f(), d.Qp = P->Qp.f(), d.Qinv = P->Qinv.f(), d.Kp = P->Kp.f();
+    d.theta = P->theta.f(), d.GQ = P->GQ.f();
+    d.Fp1 = P->Fp1.f(), d.Fp2 = P->Fp2.f(), d.Fp3 = P->Fp3.f();
+    d.Mp1 = P->Mp1.f(), d.Mp2 = P->Mp2.f(), d.Mp3 = P->Mp3.f();
+    d.Mp4 = P->Mp4.f(), d.Mp5 = P->Mp5.f(), d.Mp6 = P->Mp6.f();
+    *out = P.release();
+    return PQP_OK;
+}
+
+int pqp_plant_destroy(pqp_plant* p) {
+    if (!p) return PQP_OK;
+    DeviceGuard on(p->dev);
+    delete p;
+    return PQP_OK;
+}
+
+int pqp_plant_get(pqp_plant* p, float* Qd, float* Qp, float* theta) {
+    if (!p) return set_error(PQP_ERR_ARG, "pqp_plant_get: null plant");
+    DeviceGuard on(p->dev);
+    PQP_TRY(ensure_device());
+    hipStream_t s = lib_stream();
+    if (Qd) PQP_TRY(download(Qd, p->Qd.p, (size_t)p->N * p->N, s));
+    if (Qp) PQP_TRY(download(Qp, p->Qp.p, (size_t)p->M * p->M, s));
+    if (theta) PQP_TRY(download(theta, p->theta.p, p->N, s));
+    PQP_HIP(hipStreamSynchronize(s));
+    return PQP_OK;
+}
+
+long long pqp_plant_max_updates(const pqp_plant* p) {
+    if (!p) return set_error(PQP_ERR_ARG, "pqp_plant_max_updates: null plant");
+    return pqp::batch_chunk_for(p->N, p->M);
+}
+
+int pqp_plant_step(pqp_plant* p, int B, const float* d_x, const float* d_D, const float* d_Kp, int warm,
+                   long long max_updates, float* d_Y, float* d_U, long long* d_h, int* d_status, float* d_Fp,
+                   float* d_Mp, float* d_Fd, float* d_Md, float* d_Jp, float* d_Jd, void* stream) {
+    if (!p) return set_error(PQP_ERR_ARG, "pqp_plant_step: null plant");
+    if (B <= 0) return set_error(PQP_ERR_ARG, "pqp_plant_step: B = %d states", B);
+    if (!d_x || !d_D || !d_Y || !d_U) return set_error(PQP_ERR_ARG, "pqp_plant_step: null d_x, d_D, d_Y or d_U");
+    const long long cap = pqp::batch_chunk_for(p->N, p->M);
+    if (max_updates < 1 || max_updates > cap)
+        return set_error(PQP_ERR_ARG, "pqp_plant_step: max_updates = %lld is outside 1 .. %lld (pqp_plant_max_updates: "
+                                      "one launch's budget)", max_updates, cap);
+    PlantStep S{};
+    S.B = B;
+    S.warm = warm ? 1 : 0;
+    S.max_updates = max_updates;
+    S.x = d_x, S.D = d_D, S.Kp = d_Kp;
+    S.Y = d_Y, S.U = d_U, S.h = d_h, S.status = d_status;
+    S.Fp = d_Fp, S.Mp = d_Mp, S.Fd = d_Fd, S.Md = d_Md, S.Jp = d_Jp, S.Jd = d_Jd;
+    const bool pipe = g_plant_pipe != 0;
+    DeviceGuard on(p->dev);
+    PQP_HIP(launch_plant_step(p->data, S, p->slots[pipe ? 1 : 0], pipe, static_cast<hipStream_t>(stream)));
+    return PQP_OK;
+}
+
+// ---------------------------------------------------------------------------
 // 1. drop-in entry points (reference signatures)
 // ---------------------------------------------------------------------------
 void solveQuadraticDual(float* Y, float* Qd, float* Fd, float* Md, float* U, float* Qp, float* Qp_inv, float* Fp,
@@ -2219,6 +2351,8 @@ const KnobRef* find_knob(const char* key) {
         {"converge_xcds", &g_tune.converge_xcds, nullptr, nullptr},
         {"tiny_chunk", nullptr, nullptr, &g_tune.tiny_chunk},
         {"iterate_kind", &g_tune.iterate_kind, nullptr, nullptr},
+        {"plant_grid", &pqp::g_plant_grid, nullptr, nullptr},
+        {"plant_pipe", &pqp::g_plant_pipe, nullptr, nullptr},
     };
     for (const KnobRef& k : knobs)
         if (std::strcmp(k.key, key) == 0) return &k;
@@ -2284,6 +2418,15 @@ extern "C" int pqp_tune_get(const char* key, long long* value) {
     if (std::strcmp(key, "batch_chunk_for") == 0) {  // in: N << 32 | M; out: iterates per batched launch
         const long long v = *value;
         *value = pqp::batch_chunk_for((int)(v >> 32), (int)(v & 0xffffffff));
+        return PQP_OK;
+    }
+    if (std::strcmp(key, "plant_slots") == 0) {  // in: N | M << 8 | nd << 16 | ns << 24 | pipe << 32
+        // out: pqp_plant_step's workgroups resident at once on the current device (its default grid's bound)
+        const long long v = *value;
+        const int N = (int)(v & 255), M = (int)(v >> 8 & 255), nd = (int)(v >> 16 & 255), ns = (int)(v >> 24 & 255);
+        if (!pqp::plant_shape_ok(N, M, nd, ns)) return pqp::set_error(PQP_ERR_ARG, "pqp_tune_get: plant_slots of an unsupported shape");
+        PQP_TRY(pqp::ensure_device());
+        *value = pqp::plant_resident_wgs(N, M, nd, ns, (v >> 32 & 1) != 0);
         return PQP_OK;
     }
     if (std::strcmp(key, "converge_grid") == 0) {  // in: N << 32 | M

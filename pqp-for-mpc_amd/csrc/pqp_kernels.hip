@@ -5682,3 +5682,5 @@ hipError_t launch_extract_state(int B, const SolveState* st, long long* h, int* 
 // The relinearization kernels (k_relinearize and its companions) live in a file of their own and
 // are compiled into this object, so that the list of kernel objects every link line names stays as it is.
 #include "pqp_relin.hip"
+// So does the resident-plant control step (k_plant_step).
+#include "pqp_plant.hip"

@@ -14,6 +14,7 @@ Layers
   * status API: solve_dual, update, read_example, run_example
   * batched device API (torch tensors as device memory): :class:`Batch`,
     :class:`ProblemBatch`, :func:`mpc_batch`, :func:`mpc_restate`, :func:`horizon_batch`
+  * one plant at many states, a control step in one launch: :class:`Plant`
   * row blocks of one large problem (row-sharded solve): :class:`RowBlock`
     (driver in :mod:`pqp_amd.rowshard`)
 """
@@ -99,6 +100,12 @@ SIGNATURES = {
     "pqp_batch_relinearize": (C.c_int, [C.c_int] * 3 + [_vp] * 7 + [_vp]),
     "pqp_batch_solve_from": (C.c_int, [C.c_int] * 3 + [_vp] * 14 + [C.c_int, C.c_longlong, C.c_longlong]
                              + [_vp] * 4 + [_vp, _vp]),
+    "pqp_plant_supported": (C.c_int, [C.c_int] * 4),
+    "pqp_plant_create": (C.c_int, [C.c_int] * 5 + [_fp] * 12 + [C.POINTER(C.c_void_p)]),
+    "pqp_plant_destroy": (C.c_int, [_vp]),
+    "pqp_plant_get": (C.c_int, [_vp, _fp, _fp, _fp]),
+    "pqp_plant_max_updates": (C.c_longlong, [_vp]),
+    "pqp_plant_step": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_longlong] + [_vp] * 10 + [_vp]),
     "pqp_rowblock_create": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, C.POINTER(C.c_void_p)]),
     "pqp_rowblock_update": (C.c_int, [_vp, _vp, _vp, _vp]),
     "pqp_rowblock_check": (C.c_int, [_vp, _vp]),
@@ -812,6 +819,140 @@ class ProblemBatch:
         else:
             _check(lib().pqp_batch_solve_prepared(*args, self._s()))
         return self
+
+
+class Plant:
+    """One plant resident on the device, and a control step of B states in
+    ONE asynchronous launch (pqp_plant_* of include/pqp.h, section 2f): Fp, Mp,
+    Fd, Md of every state, then the converge solve, cold or from the previous
+    step's Y.  Every state's numbers are those of ``mpc_batch`` /
+    ``mpc_restate`` followed by ``ProblemBatch.solve`` bit for bit; the
+    plant's matrices are kept once, not B times.  Shapes: N, M <= 32,
+    N + M < 64, nd, ns <= 64 (``Plant.supported``); others raise with the
+    library's message -- use :class:`ProblemBatch` for them.
+
+    ``arrays``: Qp_inv, Gp, Kp, Fp1, Fp2, Fp3, Mp1 ... Mp6 in the reference's
+    layouts (read_example's), and optionally D (the disturbance ``step`` uses
+    when it is given none)."""
+
+    PLANT = ("Qp_inv", "Gp", "Kp", "Fp1", "Fp2", "Fp3", "Mp1", "Mp2", "Mp3", "Mp4", "Mp5", "Mp6")
+    OUT = ("Y", "U", "h", "status", "Fp", "Mp", "Fd", "Md", "Jp", "Jd")
+
+    def __init__(self, N: int, M: int, nd: int, ns: int, device=None, **arrays):
+        import torch
+
+        self.torch = torch
+        self.N, self.M, self.nd, self.ns = int(N), int(M), int(nd), int(ns)
+        self._h = None
+        self.B = 0
+        sizes = dict(Qp_inv=M * M, Gp=N * M, Kp=N, Fp1=M * nd, Fp2=M * ns, Fp3=M, Mp1=ns * ns, Mp2=nd * ns,
+                     Mp3=nd * nd, Mp4=ns, Mp5=nd, Mp6=1)
+        host = {}
+        for k in self.PLANT:
+            if k not in arrays:
+                raise ValueError(f"Plant: missing array {k}")
+            host[k] = _f32(arrays[k]).reshape(-1)
+            if host[k].size != sizes[k] and lib().pqp_plant_supported(self.N, self.M, self.nd, self.ns):
+                raise ValueError(f"Plant: {k} has {host[k].size} values, not {sizes[k]}")
+        self._D = _f32(arrays["D"]).reshape(-1) if arrays.get("D") is not None else None
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        h = C.c_void_p()
+        dev = self.device.index if self.device.index is not None else -1
+        _check(lib().pqp_plant_create(dev, self.N, self.M, self.nd, self.ns, *[_buf(host[k]) for k in self.PLANT],
+                                      C.byref(h)))
+        self._h = h
+        self.max_updates = int(lib().pqp_plant_max_updates(h))
+        self._Dt = None
+
+    @staticmethod
+    def supported(N: int, M: int, nd: int, ns: int) -> bool:
+        return bool(lib().pqp_plant_supported(int(N), int(M), int(nd), int(ns)))
+
+    @classmethod
+    def from_example(cls, directory, device=None) -> "Plant":
+        """The bundled plant's files (example/*.txt); their D is the default disturbance."""
+        E = read_example(directory)
+        return cls(E["N"], E["M"], E["nd"], E["ns"], device=device, D=E["D"], **{k: E[k] for k in cls.PLANT})
+
+    def derived(self) -> dict:
+        """Host copies of what create derived: Qd [N*N], Qp [M*M], theta [N]."""
+        out = dict(Qd=np.zeros(self.N * self.N, np.float32), Qp=np.zeros(self.M * self.M, np.float32),
+                   theta=np.zeros(self.N, np.float32))
+        _check(lib().pqp_plant_get(self._h, _buf(out["Qd"]), _buf(out["Qp"]), _buf(out["theta"])))
+        return out
+
+    def _dev(self, a, cols: int, what: str):
+        torch = self.torch
+        if not torch.is_tensor(a):
+            a = np.ascontiguousarray(np.asarray(a, np.float32))
+        t = torch.as_tensor(a, dtype=torch.float32, device=self.device).reshape(-1, cols).contiguous()
+        if t.shape[0] != self.B:
+            raise ValueError(f"Plant.step: {what} must be [{self.B}, {cols}]")
+        return t
+
+    def step(self, x, D=None, Kp=None, warm: bool = False, floor: float | None = None, max_updates: int | None = None):
+        """One control step at states ``x`` [B, ns] (numpy or a device tensor;
+        a contiguous float32 tensor on the plant's device is used in place):
+        fills the device tensors Y, U, h, status, Fp, Mp, Fd, Md, Jp, Jd and
+        returns self.  One launch on torch's current stream, no
+        synchronisation: the tensors are ready when the stream reaches them.
+
+        D [B, nd]: per-state disturbances (None: the plant's own D for every
+        state).  Kp [B, N]: per-state bounds (None: the plant's).  warm: start
+        from the rows of ``self.Y`` (the previous step's, or what the caller
+        put there) instead of Y = 1000.  floor: ``self.Y.clamp_min_(floor)``
+        first, and warm (see ProblemBatch.solve).  max_updates: at most
+        ``self.max_updates`` (one launch's budget), the default."""
+        torch = self.torch
+        f = dict(dtype=torch.float32, device=self.device)
+        B = int(x.shape[0]) if hasattr(x, "shape") and len(x.shape) == 2 else len(x)
+        if B != self.B:
+            if B <= 0:
+                _check(lib().pqp_plant_step(self._h, B, *([None] * 3), 0, 1, *([None] * 10), None))
+            self.B = B
+            self.Y, self.U = torch.zeros(B, self.N, **f), torch.zeros(B, self.M, **f)
+            self.h = torch.zeros(B, dtype=torch.int64, device=self.device)
+            self.status = torch.zeros(B, dtype=torch.int32, device=self.device)
+            self.Fp, self.Fd = torch.zeros(B, self.M, **f), torch.zeros(B, self.N, **f)
+            self.Mp, self.Md, self.Jp, self.Jd = (torch.zeros(B, **f) for _ in range(4))
+            self._Dt = None
+        xt = self._dev(x, self.ns, "x")
+        if D is None:
+            if self._D is None:
+                raise ValueError("Plant.step: this plant has no default D")
+            if self._Dt is None:
+                self._Dt = torch.as_tensor(np.tile(self._D, (B, 1)), **f).contiguous()
+            Dt = self._Dt
+        else:
+            Dt = self._dev(D, self.nd, "D")
+        Kt = None if Kp is None else self._dev(Kp, self.N, "Kp")
+        if floor is not None:
+            warm = True
+            self.Y.clamp_min_(float(floor))
+        p = ProblemBatch._p
+        cap = self.max_updates if max_updates is None else int(max_updates)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._inputs = (xt, Dt, Kt)  # alive until the next step: the launch is asynchronous
+        _check(lib().pqp_plant_step(self._h, B, p(xt), p(Dt), None if Kt is None else p(Kt), int(bool(warm)), cap,
+                                    *[p(getattr(self, k)) for k in self.OUT], stream))
+        return self
+
+    def close(self):
+        if self._h is not None:
+            lib().pqp_plant_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def perturbed_states(x, B: int, seed: int = 5, rel: float = 0.05) -> np.ndarray:

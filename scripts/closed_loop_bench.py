@@ -1,11 +1,15 @@
 #!/usr/bin/env python3
 """Closed-loop (receding-horizon) step time: K control steps, each step's full
-work, three routes per workload, alternating, R repeats.
+work, three routes per workload (five in the bundled one), alternating, R repeats.
 
   (a) the route without relinearization: new Fp / Mp, Gauss_Jordan,
       convertToDual (Qd again), pqp_batch_prepare, a cold solve
   (b) mpc_restate / relinearize (Fd, Md only), a cold solve
   (c) the same, a solve from the previous step's Y
+  (d) bundled workload only: Plant.step(warm=True), the whole step in one
+      launch on the resident plant; (d-cold) Plant.step().  Both also with the
+      software-pipelined iteration (plant_pipe = 1), and the launch alone by
+      device events.  The run checks that (d)'s last Y, U, h are (c)'s bits.
 
 Workloads: B bundled-plant instances at perturbed states (each step its own
 states, converge mode to the stop), and B synthetic problems at (N, M) whose
@@ -84,8 +88,37 @@ def bundled(torch, B, K, R):
     def route_c(k):
         pqp_amd.mpc_restate(pc, EXAMPLE, xs[k]).solve(max_updates=100000, warm=True)
 
+    # (d): the resident plant, one launch per step; one Plant per route (each keeps its own Y)
+    plants = {name: pqp_amd.Plant.from_example(EXAMPLE).step(x0)
+              for name in ("d_plant_warm", "d_cold_plant", "d_plant_warm_pipelined", "d_cold_plant_pipelined")}
+
+    def plant_route(name, warm, pipe):
+        def fn(k):
+            pqp_amd.tune("plant_pipe", pipe)
+            plants[name].step(xs[k], warm=warm)  # cap: one launch's budget (94419 here)
+        return fn
+
     res = run_routes(torch, {"a_full_setup_cold": route_a, "b_relinearize_cold": route_b,
-                             "c_relinearize_warm": route_c}, K, R)
+                             "c_relinearize_warm": route_c,
+                             "d_plant_warm": plant_route("d_plant_warm", True, 0),
+                             "d_cold_plant": plant_route("d_cold_plant", False, 0),
+                             "d_plant_warm_pipelined": plant_route("d_plant_warm_pipelined", True, 1),
+                             "d_cold_plant_pipelined": plant_route("d_cold_plant_pipelined", False, 1)}, K, R)
+    pqp_amd.tune("plant_pipe", 0)
+    pd = plants["d_plant_warm"]
+    bits = lambda t: t.cpu().numpy().view(np.uint32)  # noqa: E731
+    res["plant"] = dict(
+        d_equals_c_bits=bool(np.array_equal(bits(pd.Y), bits(pc.Y)) and np.array_equal(bits(pd.U), bits(pc.U))
+                             and np.array_equal(pd.h.cpu().numpy(), pc.h.cpu().numpy())),
+        d_cold_equals_b_bits=bool(np.array_equal(bits(plants["d_cold_plant"].Y), bits(pb.Y))
+                                  and np.array_equal(plants["d_cold_plant"].h.cpu().numpy(), pb.h.cpu().numpy())),
+        pipelined_equals_plain_bits=bool(np.array_equal(bits(plants["d_plant_warm_pipelined"].Y), bits(pd.Y))
+                                         and np.array_equal(bits(plants["d_cold_plant_pipelined"].Y),
+                                                            bits(plants["d_cold_plant"].Y))),
+        resident_workgroups={form: pqp_amd.tune_get("plant_slots", pa.N | pa.M << 8 | E["nd"] << 16 | E["ns"] << 24
+                                                    | pipe << 32) for form, pipe in (("plain", 0), ("pipelined", 1))},
+        launch_alone_us=plant_alone(torch, pd, plants["d_cold_plant"], xs))
+    res["plant"]["grid"] = {form: min(B, g) for form, g in res["plant"]["resident_workgroups"].items()}
     # what the last step of each route computed
     ha, hb, hc = (q.h.cpu().numpy() for q in (pa, pb, pc))
     same = bool(np.array_equal(ha, hb) and
@@ -94,6 +127,29 @@ def bundled(torch, B, K, R):
                         warm_h_max=int(hc.max()), all_stopped=bool((pc.status.cpu().numpy() == 1).all()))
     res["shape"] = dict(B=B, N=pa.N, M=pa.M)
     return res
+
+
+def plant_alone(torch, warm_plant, cold_plant, xs, launches=20):
+    """pqp_plant_step by device events, back to back: the warm step (every
+    launch from the Y the one before left: h = 1) and the cold one, both forms."""
+    out = {}
+    for name, pl, warm in (("warm", warm_plant, True), ("cold", cold_plant, False)):
+        for form, pipe in (("plain", 0), ("pipelined", 1)):
+            pqp_amd.tune("plant_pipe", pipe)
+            ts = []
+            for _ in range(5):
+                for i in range(3):
+                    pl.step(xs[i % len(xs)], warm=warm)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for i in range(launches):
+                    pl.step(xs[i % len(xs)], warm=warm)
+                e1.record()
+                e1.synchronize()
+                ts.append(e0.elapsed_time(e1) * 1e3 / launches)
+            out[f"{name}_{form}"] = dict(us_per_launch_median=statistics.median(ts), us_min=min(ts), us_max=max(ts))
+    pqp_amd.tune("plant_pipe", 0)
+    return out
 
 
 def synthetic(torch, B, N, M, K, R, cap):
