@@ -20,6 +20,16 @@
  *   QdT   [B][N][ldq]  Qd stored column-major per instance: element (i,k)
  *                      of Qd is QdT[b*qstride + k*ldq + i]; ldq >= N, ldq % 4 == 0
  *   theta, Fd, Y       [B][ldv] fp32 vectors, ldv >= N
+ *
+ * Padding belongs to the caller.  The layout has three kinds of it: rows
+ * N..ldq-1 of each column k < N, the stride gap [N*ldq, qstride) after each
+ * problem (qstride >= N*ldq, qstride % 4 == 0), and the vector tails [N, ldv)
+ * (no alignment rule on ldv: an odd one is fine).  None of them is ever read
+ * into a result -- they may hold anything, NaN included -- and none is
+ * written, with two exceptions: pqp_batch_generate and pqp_batch_pack store +0
+ * in the padded rows, and pqp_batch_generate stores +0 in Fd's tail.  d_Y0 of
+ * pqp_batch_iterate may be NULL, a separate buffer, or d_Y itself
+ * (tests/test_gpu_layout.py pins all of this).
  */
 #ifndef PQP_H
 #define PQP_H
@@ -199,7 +209,9 @@ int pqp_run_example(const char *dir, void *out);
  * number inst0+b of `seed`; primal Qp_inv = diag(0.1+u), Gp in {-1,0,1},
  * Kp = 10u, Fp = 20u-10, Mp = 1, converted to the dual with
  * convertToDual's exact arithmetic.  Writes QdT (column-major, padded rows
- * zeroed), Fd, Md (may be NULL) and theta. */
+ * zeroed), Fd, Md (may be NULL) and theta.  Of the padding it writes +0 into
+ * the padded rows N..ldq-1 of QdT and into Fd's tail [N, ldv); the stride gap
+ * [N*ldq, qstride) and theta's tail [N, ldv) are left as the caller had them. */
 int pqp_batch_generate(uint32_t seed, long long inst0, int B, int N, int M, float *d_QdT, int ldq,
                        long long qstride, float *d_Fd, float *d_Md, float *d_theta, int ldv, void *stream);
 

@@ -543,17 +543,22 @@ class Batch:
 
     QdT is [B][N][ldq] fp32 with Qd stored column-major per problem (element
     (i,k) at k*ldq + i); theta/Fd/Y are [B][ldv].  All launches go to torch's
-    current HIP stream of ``device``.
+    current HIP stream of ``device``.  ``qstride`` (floats between two
+    problems' QdT, a multiple of 4, default N*ldq: back to back) leaves a gap
+    after each problem that no call reads or writes.
     """
 
-    def __init__(self, B: int, N: int, device=None, ldq: int | None = None, ldv: int | None = None):
+    def __init__(self, B: int, N: int, device=None, ldq: int | None = None, ldv: int | None = None,
+                 qstride: int | None = None):
         import torch
 
         self.torch = torch
         self.B, self.N = int(B), int(N)
         self.ldq = int(ldq) if ldq else round_up(self.N, 4)
         self.ldv = int(ldv) if ldv else round_up(self.N, 4)
-        self.qstride = self.N * self.ldq
+        self.qstride = int(qstride) if qstride else self.N * self.ldq
+        if self.qstride < self.N * self.ldq or self.qstride % 4:
+            raise ValueError("qstride must be >= N*ldq and a multiple of 4")
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         kw = dict(dtype=torch.float32, device=self.device)
         self.QdT = torch.empty(self.B * self.qstride, **kw)
@@ -622,7 +627,7 @@ class Batch:
 
     def qd_rowmajor(self, b: int) -> np.ndarray:
         """Problem b's Qd back in the reference's row-major layout (host)."""
-        qt = self.QdT[b * self.qstride:(b + 1) * self.qstride].reshape(self.N, self.ldq)[:, : self.N]
+        qt = self.QdT[b * self.qstride:b * self.qstride + self.N * self.ldq].reshape(self.N, self.ldq)[:, : self.N]
         return qt.t().contiguous().cpu().numpy().reshape(-1)
 
 

@@ -63,7 +63,22 @@ int main() {
                                nullptr),
               PQP_ERR_ARG);
     EXPECT_RC(pqp_update_host(Qd.data(), Fd.data(), Fd.data(), Y.data(), Y.data(), 0), PQP_ERR_ARG);
-    if (g_fail) {
+    // the layout rules of the batched device API (pqp.h 2b), checked before any device is looked for:
+    // {B, ldq, qstride, ldv, byte offset of QdT} around the legal (2, 8, 64, 8, 0) at n = 8
+    alignas(16) static float q[2 * 64 + 4], v[2 * 8], w[2 * 8];
+    const int n = 8;
+    const long long bad[][5] = {{2, 10, 80, 8, 0}, {2, 8, 60, 8, 0}, {2, 8, 66, 8, 0}, {2, 8, 64, 7, 0},
+                                {2, 8, 64, 8, 4}, {0, 8, 64, 8, 0}, {-1, 8, 64, 8, 0}};
+    for (const auto& c : bad) {
+        const int B = (int)c[0], ldq = (int)c[1], ldv = (int)c[3];
+        const long long qs = c[2];
+        float* qd = reinterpret_cast<float*>(reinterpret_cast<char*>(q) + c[4]);
+        EXPECT_RC(pqp_batch_generate(1, 0, B, n, 4, qd, ldq, qs, v, nullptr, w, ldv, nullptr), PQP_ERR_ARG);
+        if (ldv >= n) EXPECT_RC(pqp_batch_pack(B, n, Qd.data(), qd, ldq, qs, nullptr), PQP_ERR_ARG);
+        EXPECT_RC(pqp_batch_theta(B, n, qd, ldq, qs, v, ldv, nullptr), PQP_ERR_ARG);
+        EXPECT_RC(pqp_batch_update(B, n, qd, ldq, qs, v, v, ldv, v, w, nullptr), PQP_ERR_ARG);
+        EXPECT_RC(pqp_batch_iterate(B, n, qd, ldq, qs, v, v, ldv, nullptr, w, 3, nullptr), PQP_ERR_ARG);
+    }    if (g_fail) {
         std::fprintf(stderr, "%d case(s) failed\n", g_fail);
         return 1;
     }

@@ -261,3 +261,54 @@ def test_tuning_knobs_roundtrip():
     assert L.pqp_tune_last_path(C.byref(fb)) == 0 and fb.value == 0
     assert L.pqp_tune_converge_grid(1024, 512) > 0 and L.pqp_tune_converge_grid(28, 7) > 0
     assert pqp_amd.tune_get("last_batch_kernel") == 0  # no path-2 launch on this thread yet
+
+
+# ---------------------------------------------------------------------------
+# layout rejections of the batched device API (pqp.h 2b): check_batch returns
+# before it looks for a device, so these run without one.  Nothing is
+# dereferenced: the pointers are dummy addresses.
+# ---------------------------------------------------------------------------
+_DUMMY = 0x10000  # non-null, 16-byte aligned
+_BAD_LAYOUTS = {  # case -> (overrides of the legal B=2, N=8, ldq=8, qstride=64, ldv=8, QdT=_DUMMY; the argument named)
+    "ldq_not_multiple_of_4": (dict(ldq=10, qstride=80), "ldq"),
+    "qstride_below_N_ldq": (dict(qstride=60), "qstride"),
+    "qstride_not_multiple_of_4": (dict(qstride=66), "qstride"),
+    "ldv_below_N": (dict(ldv=7), "ldv"),
+    "QdT_offset_by_4_bytes": (dict(QdT=_DUMMY + 4), "QdT"),
+    "B_zero": (dict(B=0), "B="),
+    "B_negative": (dict(B=-1), "B="),
+}
+
+
+def _batch_call(L, fn, a):
+    import ctypes as C
+
+    p, q = C.c_void_p(_DUMMY), C.c_void_p(a["QdT"])
+    B, N, ldq, qs, ldv = a["B"], a["N"], a["ldq"], a["qstride"], a["ldv"]
+    if fn == "pqp_batch_generate":
+        return L.pqp_batch_generate(1, 0, B, N, 4, q, ldq, qs, p, p, p, ldv, None)
+    if fn == "pqp_batch_pack":
+        return L.pqp_batch_pack(B, N, p, q, ldq, qs, None)
+    if fn == "pqp_batch_theta":
+        return L.pqp_batch_theta(B, N, q, ldq, qs, p, ldv, None)
+    if fn == "pqp_batch_update":
+        return L.pqp_batch_update(B, N, q, ldq, qs, p, p, ldv, p, C.c_void_p(_DUMMY + 4096), None)
+    return L.pqp_batch_iterate(B, N, q, ldq, qs, p, p, ldv, None, p, 3, None)
+
+
+_BATCH_FNS = ["pqp_batch_generate", "pqp_batch_pack", "pqp_batch_theta", "pqp_batch_update", "pqp_batch_iterate"]
+
+
+@pytest.mark.parametrize("fn,case", [(f, c) for f in _BATCH_FNS for c in sorted(_BAD_LAYOUTS)
+                                     if not (f == "pqp_batch_pack" and c == "ldv_below_N")])  # pack takes no ldv
+def test_batch_layout_rejections_need_no_device(fn, case):
+    """Every layout rule of pqp.h 2b, against every entry point that takes the
+    layout: PQP_ERR_ARG, and pqp_last_error() names the offending argument."""
+    import pqp_amd
+
+    over, named = _BAD_LAYOUTS[case]
+    args = dict(B=2, N=8, ldq=8, qstride=64, ldv=8, QdT=_DUMMY)
+    args.update(over)
+    L = pqp_amd.lib()
+    assert _batch_call(L, fn, args) == pqp_amd.PQP_ERR_ARG
+    assert named in pqp_amd.last_error(), pqp_amd.last_error()
