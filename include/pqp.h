@@ -239,6 +239,27 @@ int pqp_batch_update(int B, int N, const float *d_QdT, int ldq, long long qstrid
 int pqp_batch_iterate(int B, int N, const float *d_QdT, int ldq, long long qstride, const float *d_theta,
                       const float *d_Fd, int ldv, const float *d_Y0, float *d_Y, int updates, void *stream);
 
+/* Per-problem bit-symmetry of Qd in the QdT layout: d_sym[b] (device, [B]; may
+ * be NULL) is nonzero iff Qd_b(i,k) and Qd_b(k,i) hold the same bits for all
+ * i, k < N (+0 and -0 differ; a NaN equals itself only with the same payload).
+ * *all_sym_out = 1 iff every problem is symmetric.  Reads entries i, k < N
+ * only: never the padded rows or the stride gap.  Synchronises `stream` (the
+ * flag comes back to the host), as pqp_batch_prepare does. */
+int pqp_batch_symmetric(int B, int N, const float *d_QdT, int ldq, long long qstride, int *d_sym, int *all_sym_out,
+                        void *stream);
+
+/* pqp_batch_iterate for a batch in which EVERY Qd is bit-symmetric (the
+ * caller's contract: pqp_batch_symmetric's all_sym_out, which holds for
+ * pqp_batch_generate and for convertToDual with a diagonal Qp_inv).  Same
+ * arguments, same d_Y0 rules (NULL, a separate buffer, or d_Y itself), same
+ * bits.  At N == ldq == 1024 each 64 x 64 tile of Qd is read from HBM once
+ * for itself and its mirror (k_batch_half); other shapes, and the tuning knob
+ * iterate_half = 0, forward to pqp_batch_iterate.  With a Qd that is not
+ * symmetric the result is that of the matrix whose upper triangle mirrors the
+ * stored lower one in some tiles: wrong, but nothing is read out of bounds. */
+int pqp_batch_iterate_sym(int B, int N, const float *d_QdT, int ldq, long long qstride, const float *d_theta,
+                          const float *d_Fd, int ldv, const float *d_Y0, float *d_Y, int updates, void *stream);
+
 /* ----------------------------------------------------------------------
  * 2c. Batched small problems: many independent MPC problems (batched
  * horizons / states), one workgroup each.  Every array holds B problems back

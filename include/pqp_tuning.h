@@ -109,6 +109,9 @@ extern "C" {
  *                          other multiples of 1024: k_batch_stream; else
  *                          k_batch_iterate), 1 k_batch_iterate, 2 k_batch_stream,
  *                          3 k_batch_resident without the register blocks
+ *   iterate_half [1]       pqp_batch_iterate_sym: 1 k_batch_half where the shape
+ *                          fits (n_dual 1024), 0 forward to pqp_batch_iterate
+ *                          (in-process A/B of the two; same bits)
  *   plant_grid [0]         pqp_plant_step: at most this many workgroups (0: every
  *                          resident wave slot), so that a small batch walks the
  *                          kernel's state loop (tests)

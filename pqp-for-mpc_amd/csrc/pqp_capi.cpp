@@ -1499,6 +1499,39 @@ int pqp_batch_iterate(int B, int N, const float* d_QdT, int ldq, long long qstri
     return PQP_OK;
 }
 
+int pqp_batch_iterate_sym(int B, int N, const float* d_QdT, int ldq, long long qstride, const float* d_theta,
+                          const float* d_Fd, int ldv, const float* d_Y0, float* d_Y, int updates, void* stream) {
+    PQP_TRY(check_batch(B, N, d_QdT, ldq, qstride, ldv));
+    if (!d_theta || !d_Fd || !d_Y || updates < 0)
+        return set_error(PQP_ERR_ARG, "pqp_batch_iterate_sym: bad argument");
+    if ((size_t)2 * ldq * sizeof(float) > 160 * 1024)
+        return set_error(PQP_ERR_ARG, "pqp_batch_iterate_sym: ldq=%d needs more than 160 KiB of LDS", ldq);
+    PQP_HIP(launch_batch_iterate_sym(B, d_QdT, qstride, ldq, N, d_theta, d_Fd, ldv, d_Y0, d_Y, updates,
+                                     static_cast<hipStream_t>(stream)));
+    return PQP_OK;
+}
+
+int pqp_batch_symmetric(int B, int N, const float* d_QdT, int ldq, long long qstride, int* d_sym, int* all_sym_out,
+                        void* stream) {
+    if (all_sym_out) *all_sym_out = 0;
+    PQP_TRY(check_batch(B, N, d_QdT, ldq, qstride, N));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    DevBuf own;  // the flags, where the caller keeps none
+    int* sym = d_sym;
+    if (!sym) {
+        PQP_TRY(own.alloc(sizeof(int) * (size_t)B));
+        sym = static_cast<int*>(own.p);
+    }
+    PQP_HIP(launch_check_symmetric_ld(B, d_QdT, N, ldq, qstride, sym, s));
+    std::vector<int> flags((size_t)B);
+    PQP_HIP(hipMemcpyAsync(flags.data(), sym, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, s));
+    PQP_HIP(hipStreamSynchronize(s));
+    bool all_sym = true;
+    for (int v : flags) all_sym = all_sym && v != 0;
+    if (all_sym_out) *all_sym_out = all_sym ? 1 : 0;
+    return PQP_OK;
+}
+
 // ---------------------------------------------------------------------------
 // 2d. row blocks of one large problem (row-sharded solve)
 // ---------------------------------------------------------------------------
@@ -2351,6 +2384,7 @@ const KnobRef* find_knob(const char* key) {
         {"converge_xcds", &g_tune.converge_xcds, nullptr, nullptr},
         {"tiny_chunk", nullptr, nullptr, &g_tune.tiny_chunk},
         {"iterate_kind", &g_tune.iterate_kind, nullptr, nullptr},
+        {"iterate_half", &g_tune.iterate_half, nullptr, nullptr},
         {"plant_grid", &pqp::g_plant_grid, nullptr, nullptr},
         {"plant_pipe", &pqp::g_plant_pipe, nullptr, nullptr},
     };

@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "pqp_device.h"
+#include "pqp_halfsched.h"
 #include "pqp_launch.h"
 
 namespace pqp {
@@ -445,6 +446,150 @@ __global__ void __launch_bounds__(256) k_batch_resident(const float* __restrict_
     }
     const float* fin = (updates & 1) ? yb : ya;
     for (int i = tid; i < N; i += 256) Y[(size_t)b * ldv + i] = fin[i];
+}
+
+// ---------------------------------------------------------------------------
+// k_batch_half (n_dual 1024, every Qd bit-symmetric): each 64 x 64 tile of Qd
+// is read from HBM once for itself and its mirror.  One workgroup of 16 waves
+// per problem, wave I owning rows 64 I .. 64 I + 63 (one row per lane), on the
+// skewed schedule of pqp_halfsched.h: at step T wave I sums k-block K = (T - I)
+// mod 16 while wave K sums k-block I, both from one copy of tile (min, max) in
+// LDS that each of them loaded half of (a wave on a diagonal tile loads all of
+// its own).  Rows of stride 65 words make the straight read (the lower wave)
+// and the transposed one (the higher wave, Qd(k, i) for Qd(i, k)) free of bank
+// conflicts.  Per step: the half-tile prefetched in registers goes to LDS,
+// barrier, the next step's loads are issued, 64 k are summed with y broadcast
+// from LDS, and a wave past its k-block 15 applies the update into the other y
+// buffer; barrier.  Every row adds lean4's / literal1's terms in k = 0 .. N-1
+// order, so the bits are k_batch_resident's (up to the sign and payload of a
+// NaN result, which no two of these kernels share: it follows the operand order
+// the compiler picks for each add).  The only synchronisation is the
+// workgroup barrier, which every wave reaches in every step.
+// ---------------------------------------------------------------------------
+// lean4's expressions for one row
+__device__ __forceinline__ void lean1(float& ap, float& an, float q, float y) {
+    const float z = 0.0f * y;  // (+0)*y: +0 for finite y >= 0, NaN for inf/NaN y
+    const float p = q * y;
+    ap += (q < 0.0f) ? z : p;
+    an += (q > 0.0f) ? z : -p;
+}
+// 64 k of one tile in LDS for this lane's row: entry k at q[k * SK]; DIAG: the
+// tile holds the row's diagonal entry (k == lane): literal form with theta
+// there, as in the diagonal window of the other kernels (off the diagonal the
+// lean and the literal form give the same bits: DESIGN.md "Lean form")
+template <int SK, bool DIAG>
+__device__ __forceinline__ void half_tile_sum(float& ap, float& an, const float* __restrict__ q,
+                                              const float* __restrict__ yk, int lane, float th) {
+    // 8 k per pass: with 16 the two prefetch buffers no longer fit beside it in
+    // the 128 registers of a 16-wave workgroup (14 spilled)
+    constexpr int CH = 8;
+#pragma unroll 1
+    for (int c = 0; c < hs::kTile; c += CH) {
+        float qv[CH];
+#pragma unroll
+        for (int j = 0; j < CH; ++j) qv[j] = q[(c + j) * SK];
+#pragma unroll
+        for (int j = 0; j < CH; j += 4) {
+            const float4 yv = *reinterpret_cast<const float4*>(yk + c + j);
+            if constexpr (DIAG) {
+                literal1(ap, an, qv[j + 0], yv.x, (c + j + 0 == lane) ? th : 0.0f);
+                literal1(ap, an, qv[j + 1], yv.y, (c + j + 1 == lane) ? th : 0.0f);
+                literal1(ap, an, qv[j + 2], yv.z, (c + j + 2 == lane) ? th : 0.0f);
+                literal1(ap, an, qv[j + 3], yv.w, (c + j + 3 == lane) ? th : 0.0f);
+            } else {
+                lean1(ap, an, qv[j + 0], yv.x);
+                lean1(ap, an, qv[j + 1], yv.y);
+                lean1(ap, an, qv[j + 2], yv.z);
+                lean1(ap, an, qv[j + 3], yv.w);
+            }
+        }
+    }
+}
+constexpr size_t kHalfLdsBytes = ((size_t)2 * 1024 + (size_t)hs::kSlots * hs::kTileWords) * sizeof(float);
+__global__ void __launch_bounds__(1024) k_batch_half(const float* __restrict__ QdT, long long qstride, int ldq,
+                                                     const float* __restrict__ theta, const float* __restrict__ Fd,
+                                                     int ldv, const float* Y0, float* Y, int updates) {
+    constexpr int N = 1024;
+    constexpr int HL = hs::kHalfCols / 4;  // 16-byte loads per lane and half: one covers 4 rows of one k
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float* ybuf = lds;           // [2][N]: update h reads hs::y_read_buf(h), writes the other
+    float* tiles = lds + 2 * N;  // [hs::kSlots][hs::kTileWords]
+    const int b = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const float* Q = QdT + (size_t)b * (size_t)qstride;
+    const int row = hs::kTile * wave + lane;
+    // Y0 may alias Y: this problem's Y0 is in LDS before any of its Y is written
+    ybuf[tid] = Y0 ? Y0[(size_t)b * ldv + tid] : 1000.0f;  // initMat(Y,1000) :710
+    ybuf[N + tid] = 0.0f;
+    const float th = theta[(size_t)b * ldv + row];
+    const float f = Fd[(size_t)b * ldv + row];
+    // this lane's part of a tile: rows lr .. lr + 3 of k lk, lk + 4, ...
+    const int lk = lane >> 4, lr = 4 * (lane & 15);
+    f32x4 pa[HL], pb[HL];  // pa: this wave's half (the first of a diagonal tile), pb: a diagonal tile's second
+    auto issue = [&](int T) {  // step T's loads (non-temporal: every tile is read once per update)
+        const int halves = hs::load_halves(T, wave, updates);
+        if (halves == 0) return;
+        const int k0 = hs::kTile * hs::tile_cols(T, wave) + hs::first_half_col(halves) + lk;
+        const float* src = Q + (size_t)k0 * ldq + hs::kTile * hs::tile_rows(T, wave) + lr;
+#pragma unroll
+        for (int j = 0; j < HL; ++j)
+            pa[j] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src + (size_t)(4 * j) * ldq));
+        if (halves == 3) {
+#pragma unroll
+            for (int j = 0; j < HL; ++j)
+                pb[j] = __builtin_nontemporal_load(
+                    reinterpret_cast<const f32x4*>(src + (size_t)(hs::kHalfCols + 4 * j) * ldq));
+        }
+    };
+    auto stash = [&](int T) {  // the loaded halves into the pair's slot, entry (i, k) at k * 65 + i
+        const int halves = hs::load_halves(T, wave, updates);
+        if (halves == 0) return;
+        float* dst = tiles + hs::slot(T, wave) * hs::kTileWords + (hs::first_half_col(halves) + lk) * hs::kTileStride + lr;
+#pragma unroll
+        for (int j = 0; j < HL; ++j) {
+            float* d = dst + 4 * j * hs::kTileStride;
+            d[0] = pa[j].x, d[1] = pa[j].y, d[2] = pa[j].z, d[3] = pa[j].w;
+        }
+        if (halves == 3) {
+#pragma unroll
+            for (int j = 0; j < HL; ++j) {
+                float* d = dst + (hs::kHalfCols + 4 * j) * hs::kTileStride;
+                d[0] = pb[j].x, d[1] = pb[j].y, d[2] = pb[j].z, d[3] = pb[j].w;
+            }
+        }
+    };
+    const int S = hs::steps(updates);
+    issue(0);
+    __syncthreads();
+    if (updates == 0) Y[(size_t)b * ldv + tid] = ybuf[tid];
+    float ap = 0.0f, an = 0.0f;
+    for (int T = 0; T < S; ++T) {
+        stash(T);
+        __syncthreads();
+        issue(T + 1);  // nothing past the last step
+        if (hs::active(T, wave, updates)) {
+            const int h = hs::update_of(T, wave), K = hs::kblock_of(T, wave);
+            const float* cur = ybuf + hs::y_read_buf(h) * N;
+            const float* yk = cur + hs::kTile * K;
+            const float* tile = tiles + hs::slot(T, wave) * hs::kTileWords;
+            if (K == 0) ap = an = 0.0f;
+            if (hs::diagonal(T, wave))
+                half_tile_sum<hs::kTileStride, true>(ap, an, tile + lane, yk, lane, th);
+            else if (hs::transposed(T, wave))  // row * 65 + k
+                half_tile_sum<1, false>(ap, an, tile + lane * hs::kTileStride, yk, lane, th);
+            else  // k * 65 + row
+                half_tile_sum<hs::kTileStride, false>(ap, an, tile + lane, yk, lane, th);
+            if (hs::last_kblock(T, wave)) {
+                const float num = an + 1.0f * max_ref(0.0f, -f);  // matrixAdd(num, Fdn, 1) :611
+                const float den = ap + 1.0f * max_ref(0.0f, f);   // matrixAdd(den, Fdp, 1) :612
+                const float yn = num / den * cur[row];            // updY :594
+                ybuf[hs::y_write_buf(h) * N + row] = yn;
+                if (h == updates - 1) Y[(size_t)b * ldv + row] = yn;
+            }
+        }
+        __syncthreads();
+    }
 }
 // </hot-kernel>
 
@@ -4899,6 +5044,26 @@ static hipError_t launch_batch_iterate_one(int B, const float* QdT, long long qs
     return hipGetLastError();
 }
 
+// Every Qd bit-symmetric (the caller's contract): k_batch_half at n_dual 1024
+// under k_batch_resident's layout bounds, launch_batch_iterate otherwise or
+// with the iterate_half knob at 0.
+hipError_t launch_batch_iterate_sym(int B, const float* QdT, long long qstride, int ldq, int N, const float* theta,
+                                    const float* Fd, int ldv, const float* Y0, float* Y, int updates, hipStream_t s) {
+    if (!g_tune.iterate_half || N != 1024 || ldq != 1024 || qstride < (long long)N * ldq ||
+        qstride * 4 > 0x7fffffffLL)
+        return launch_batch_iterate(B, QdT, qstride, ldq, N, theta, Fd, ldv, Y0, Y, updates, s);
+    int done = 0;
+    do {
+        const int c = (updates - done) < kIterPerLaunch ? (updates - done) : kIterPerLaunch;
+        hipLaunchKernelGGL(k_batch_half, dim3(B), dim3(1024), kHalfLdsBytes, s, QdT, qstride, ldq, theta, Fd, ldv,
+                           done ? Y : Y0, Y, c);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        done += c;
+    } while (done < updates);
+    return hipSuccess;
+}
+
 hipError_t launch_batch_update(int B, const float* QdT, long long qstride, int ldq, int N, const float* theta,
                                const float* Fd, int ldv, const float* Yin, float* Yout, hipStream_t s) {
     const size_t lds = (size_t)ldq * sizeof(float);
@@ -5598,14 +5763,25 @@ __global__ void __launch_bounds__(256) k_check_symmetric(const float* __restrict
     }
     if (__syncthreads_or(bad) && threadIdx.x == 0) atomicAnd(sym + b, 0);
 }
-// The same for N % 4 == 0 and a 16-byte-aligned Qd: one workgroup per (problem,
-// 64-row band bi) walks the tile pairs (bi, bj >= bi) with 16-byte loads, so
-// the grid is B x N/64 workgroups instead of B x (N/32)^2 (most of which had
-// nothing to do).
-__global__ void __launch_bounds__(256) k_check_symmetric4(const float* __restrict__ Qd, int N, int* __restrict__ sym) {
+// The same for a 16-byte-aligned Qd with leading dimension ld % 4 == 0 and
+// `stride` % 4 == 0 floats between problems: one workgroup per (problem, 64-row
+// band bi) walks the tile pairs (bi, bj >= bi) with 16-byte loads, so the grid
+// is B x N/64 workgroups instead of B x (N/32)^2 (most of which had nothing to
+// do).  Only entries (i, j) with i, j < N are read: where N % 4 != 0 the last
+// columns of a row are read one by one.
+__device__ __forceinline__ uint4 sym_load4(const unsigned* __restrict__ p, int j, int N) {
+    if (j + 3 < N) return *reinterpret_cast<const uint4*>(p);
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (j + 0 < N) v.x = p[0];
+    if (j + 1 < N) v.y = p[1];
+    if (j + 2 < N) v.z = p[2];
+    return v;
+}
+__global__ void __launch_bounds__(256) k_check_symmetric4(const float* __restrict__ Qd, int N, int ld, long long stride,
+                                                          int* __restrict__ sym) {
     __shared__ unsigned tile[64][65];
     const int b = blockIdx.y, bi = blockIdx.x;
-    const unsigned* q = reinterpret_cast<const unsigned*>(Qd) + (size_t)b * N * N;
+    const unsigned* q = reinterpret_cast<const unsigned*>(Qd) + (size_t)b * (size_t)stride;
     const int nt = (N + 63) / 64;
     const int tc = (threadIdx.x & 15) * 4, tr = threadIdx.x >> 4;  // 16 rows x 4 columns per pass
     int bad = 0;
@@ -5614,7 +5790,7 @@ __global__ void __launch_bounds__(256) k_check_symmetric4(const float* __restric
         for (int pss = 0; pss < 4; ++pss) {  // tile (bj, bi), transposed into LDS
             const int r = tr + 16 * pss, i = bj * 64 + r, j = bi * 64 + tc;
             uint4 v = make_uint4(0u, 0u, 0u, 0u);
-            if (i < N && j < N) v = *reinterpret_cast<const uint4*>(q + (size_t)i * N + j);
+            if (i < N && j < N) v = sym_load4(q + (size_t)i * ld + j, j, N);
             tile[tc + 0][r] = v.x;
             tile[tc + 1][r] = v.y;
             tile[tc + 2][r] = v.z;
@@ -5625,7 +5801,7 @@ __global__ void __launch_bounds__(256) k_check_symmetric4(const float* __restric
         for (int pss = 0; pss < 4; ++pss) {  // against tile (bi, bj)
             const int r = tr + 16 * pss, i = bi * 64 + r, j = bj * 64 + tc;
             if (i < N && j < N) {
-                const uint4 v = *reinterpret_cast<const uint4*>(q + (size_t)i * N + j);
+                const uint4 v = sym_load4(q + (size_t)i * ld + j, j, N);
                 bad |= (v.x != tile[r][tc + 0]) | (v.y != tile[r][tc + 1]) | (v.z != tile[r][tc + 2]) |
                        (v.w != tile[r][tc + 3]);
             }
@@ -5634,23 +5810,30 @@ __global__ void __launch_bounds__(256) k_check_symmetric4(const float* __restric
     }
     if (__syncthreads_or(bad) && threadIdx.x == 0) atomicAnd(sym + b, 0);
 }
-hipError_t launch_check_symmetric(int B, const float* Qd, int N, int* sym, hipStream_t s) {
+// sym[b] for B matrices of leading dimension ld, `stride` floats apart (a QdT
+// as well as a row-major Qd: a matrix equals its transpose in either)
+hipError_t launch_check_symmetric_ld(int B, const float* Qd, int N, int ld, long long stride, int* sym,
+                                     hipStream_t s) {
     if (B <= 0 || N <= 0) return hipSuccess;
-    const bool wide = N % 4 == 0 && ((uintptr_t)Qd & 15) == 0;
+    const bool wide = ld % 4 == 0 && stride % 4 == 0 && ((uintptr_t)Qd & 15) == 0;
+    if (!wide && (ld != N || stride != (long long)N * N)) return hipErrorInvalidValue;
     hipError_t e = hipSuccess;
     for (int b0 = 0; b0 < B && e == hipSuccess; b0 += 65535) {
         const int nb = (B - b0) < 65535 ? (B - b0) : 65535;
         e = hipMemsetAsync(sym + b0, 0x01, sizeof(int) * nb, s);  // bytes 0x01: nonzero = symmetric
         if (e != hipSuccess) break;
         if (wide)
-            hipLaunchKernelGGL(k_check_symmetric4, dim3(cdiv(N, 64), nb), dim3(256), 0, s, Qd + (size_t)b0 * N * N, N,
-                               sym + b0);
+            hipLaunchKernelGGL(k_check_symmetric4, dim3(cdiv(N, 64), nb), dim3(256), 0, s,
+                               Qd + (size_t)b0 * (size_t)stride, N, ld, stride, sym + b0);
         else
             hipLaunchKernelGGL(k_check_symmetric, dim3(cdiv(N, 32), cdiv(N, 32), nb), dim3(256), 0, s,
                                Qd + (size_t)b0 * N * N, N, sym + b0);
         e = hipGetLastError();
     }
     return e;
+}
+hipError_t launch_check_symmetric(int B, const float* Qd, int N, int* sym, hipStream_t s) {
+    return launch_check_symmetric_ld(B, Qd, N, N, (long long)N * N, sym, s);
 }
 
 __global__ void k_extract_state(int B, const SolveState* __restrict__ st, long long* __restrict__ h,

@@ -62,9 +62,14 @@ hipError_t launch_poison_lds(int bits, int* seen, int cus, hipStream_t s);
 hipError_t launch_transpose_b(int B, const float* src, int rows, int cols, float* dst, hipStream_t s);
 // sym[b] = nonzero iff problem b's row-major Qd equals its transpose bit for bit
 hipError_t launch_check_symmetric(int B, const float* Qd, int N, int* sym, hipStream_t s);
+// the same for leading dimension ld and `stride` floats between problems (both % 4 == 0, Qd 16-byte aligned)
+hipError_t launch_check_symmetric_ld(int B, const float* Qd, int N, int ld, long long stride, int* sym, hipStream_t s);
 
 hipError_t launch_batch_iterate(int B, const float* QdT, long long qstride, int ldq, int N, const float* theta,
                                 const float* Fd, int ldv, const float* Y0, float* Y, int updates, hipStream_t s);
+// every Qd bit-symmetric: k_batch_half where the shape fits (n_dual 1024), else launch_batch_iterate
+hipError_t launch_batch_iterate_sym(int B, const float* QdT, long long qstride, int ldq, int N, const float* theta,
+                                    const float* Fd, int ldv, const float* Y0, float* Y, int updates, hipStream_t s);
 hipError_t launch_batch_update(int B, const float* QdT, long long qstride, int ldq, int N, const float* theta,
                                const float* Fd, int ldv, const float* Yin, float* Yout, hipStream_t s);
 hipError_t launch_update_split(const float* QpT, const float* QnT, int ldq, int N, const float* Fdp,
@@ -149,6 +154,7 @@ struct Tuning {  // every tuning knob of the library (pqp_tune, include/pqp_tuni
     int iterate_kind = 0;  // pqp_batch_iterate: 0 default (k_batch_resident at N 1024, k_batch_stream at other
                            // multiples of 1024, k_batch_iterate otherwise), 1 k_batch_iterate, 2 k_batch_stream,
                            // 3 k_batch_resident without its register blocks
+    int iterate_half = 1;  // pqp_batch_iterate_sym: 1 k_batch_half where the shape fits, 0 forward to pqp_batch_iterate
     int tiny_stall = 0;  // k_solve_quintet's deciding waves return at once: every wait expires (error path)
     int persist_xcds = 0;  // k_split_persist's workgroups packed onto this many XCDs (0: 4, 8: spread over all)
     int converge_xcds = 0;  // k_converge_persist's workgroups packed onto this many XCDs (0: 6, 8: spread over all)

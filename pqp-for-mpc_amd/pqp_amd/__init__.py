@@ -89,6 +89,9 @@ SIGNATURES = {
                         + [_vp]),
     "pqp_batch_solve_path": (C.c_int, [C.c_int, C.c_int]),
     "pqp_batch_solve_kernel": (C.c_int, [C.c_int, C.c_int]),
+    "pqp_batch_iterate_sym": (C.c_int, [C.c_int, C.c_int, _vp, C.c_int, C.c_longlong, _vp, _vp, C.c_int, _vp, _vp,
+                                        C.c_int, _vp]),
+    "pqp_batch_symmetric": (C.c_int, [C.c_int, C.c_int, _vp, C.c_int, C.c_longlong, _vp, C.POINTER(C.c_int), _vp]),
     "pqp_batch_prepare": (C.c_int, [C.c_int] * 3 + [_vp] * 8 + [C.POINTER(C.c_int), _vp]),
     "pqp_batch_solve_prepared": (C.c_int, [C.c_int] * 3 + [_vp] * 14 + [C.c_int, C.c_longlong, C.c_longlong]
                                  + [_vp] * 4 + [_vp]),
@@ -546,6 +549,14 @@ class Batch:
     current HIP stream of ``device``.  ``qstride`` (floats between two
     problems' QdT, a multiple of 4, default N*ldq: back to back) leaves a gap
     after each problem that no call reads or writes.
+
+    generate() and load() check once whether every problem's Qd is
+    bit-symmetric (pqp_batch_symmetric) and keep the answer in ``all_sym``;
+    iterate() then runs pqp_batch_iterate_sym, which at N = 1024 reads each
+    tile of Qd once for itself and its mirror.  One non-symmetric problem
+    sends the whole batch through pqp_batch_iterate.  A caller who writes
+    ``QdT`` directly calls qd_changed() afterwards: it clears the flag (the
+    plain kernel is right for every Qd); check_symmetric() sets it again.
     """
 
     def __init__(self, B: int, N: int, device=None, ldq: int | None = None, ldv: int | None = None,
@@ -567,6 +578,24 @@ class Batch:
         self.Md = torch.zeros(self.B, **kw)
         self.Y = torch.zeros(self.B, self.ldv, **kw)
         self.Y2 = torch.zeros(self.B, self.ldv, **kw)
+        self.all_sym = False  # every Qd bit-symmetric, as of the last generate() / load() / check_symmetric()
+
+    def check_symmetric(self):
+        """One pass over QdT (pqp_batch_symmetric; synchronises the stream):
+        sets ``all_sym`` and returns the per-problem flags (torch int32 [B])."""
+        sym = self.torch.zeros(self.B, dtype=self.torch.int32, device=self.device)
+        all_sym = C.c_int(0)
+        _check(lib().pqp_batch_symmetric(self.B, self.N, self._p(self.QdT), self.ldq, self.qstride, self._p(sym),
+                                         C.byref(all_sym), self._stream()))
+        self.all_sym = bool(all_sym.value)
+        return sym
+
+    def qd_changed(self):
+        """Tell the batch that QdT was written from outside generate() /
+        load(): iterate() goes back to pqp_batch_iterate, which assumes no
+        symmetry, until check_symmetric() says otherwise."""
+        self.all_sym = False
+        return self
 
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
@@ -582,6 +611,7 @@ class Batch:
         _check(lib().pqp_batch_generate(seed, inst0, self.B, self.N, M, self._p(self.QdT), self.ldq, self.qstride,
                                         self._p(self.Fd), self._p(self.Md), self._p(self.theta), self.ldv,
                                         self._stream()))
+        self.check_symmetric()
         return self
 
     def load(self, Qd, Fd):
@@ -598,7 +628,7 @@ class Batch:
                                     self._stream()))
         _check(lib().pqp_batch_theta(self.B, self.N, self._p(self.QdT), self.ldq, self.qstride, self._p(self.theta),
                                      self.ldv, self._stream()))
-        torch.cuda.current_stream(self.device).synchronize()  # Qd staging buffer goes out of scope
+        self.check_symmetric()  # synchronises: the Qd staging buffer goes out of scope
         return self
 
     def reset(self, value: float = 1000.0):
@@ -613,12 +643,13 @@ class Batch:
         return self
 
     def iterate(self, updates: int, from_start: bool = True):
-        """`updates` fused updates per problem in one launch (pqp_batch_iterate);
+        """`updates` fused updates per problem in one launch (pqp_batch_iterate,
+        or pqp_batch_iterate_sym where every Qd is bit-symmetric: same bits);
         from_start=True begins at the reference's Y = 1000."""
         y0 = None if from_start else self._p(self.Y)
-        _check(lib().pqp_batch_iterate(self.B, self.N, self._p(self.QdT), self.ldq, self.qstride, self._p(self.theta),
-                                       self._p(self.Fd), self.ldv, y0, self._p(self.Y2), int(updates),
-                                       self._stream()))
+        fn = lib().pqp_batch_iterate_sym if self.all_sym else lib().pqp_batch_iterate
+        _check(fn(self.B, self.N, self._p(self.QdT), self.ldq, self.qstride, self._p(self.theta), self._p(self.Fd), self.ldv, y0,
+                  self._p(self.Y2), int(updates), self._stream()))
         self.Y, self.Y2 = self.Y2, self.Y
         return self
 
