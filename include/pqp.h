@@ -506,6 +506,53 @@ int pqp_plant_step(pqp_plant *p, int B, const float *d_x, const float *d_D, cons
                    long long max_updates, float *d_Y, float *d_U, long long *d_h, int *d_status,
                    float *d_Fp, float *d_Mp, float *d_Fd, float *d_Md, float *d_Jp, float *d_Jd, void *stream);
 
+/* ----------------------------------------------------------------------
+ * 2g. The resident plant at horizon sizes.  A plant of H >= 2 stacked stages
+ * (the bundled plant: N = 28 H, M = 7 H) is past 2f's one wave per state.
+ * pqp_plant_create_horizon also takes those shapes: the same pqp_plant, whose
+ * step runs one WORKGROUP per state at a time -- the plant's matrices staged
+ * in LDS once per workgroup, only the per-state vectors refreshed between
+ * states -- still in ONE asynchronous launch.  pqp_plant_supported and
+ * pqp_plant_create accept exactly 2f's shapes as before: the new shapes are
+ * opt-in through the two names below.
+ *
+ * pqp_plant_step, pqp_plant_get, pqp_plant_max_updates and pqp_plant_destroy
+ * work on either kind of handle, and pqp_plant_step's contract holds word for
+ * word: one launch on `stream`, asynchronous, no allocation, no
+ * synchronisation, no copy to the host, the caller's device restored, so it
+ * can be chained on a stream or captured in a graph.  (The tuning key
+ * plant_pipe has no meaning for the one-workgroup step and is ignored there;
+ * plant_grid caps its grid too.)
+ *
+ * Bit-exactness, as 2f: state b of a step gives exactly what
+ * pqp_batch_compute_fp, pqp_batch_compute_mp and pqp_batch_relinearize at
+ * that state, followed by pqp_batch_solve_from in PQP_MODE_CONVERGE with the
+ * same cap (cold: d_Y0 NULL; warm: from d_Y's rows), give for problem b --
+ * Y, U, h, status, Fp, Mp, Fd, Md, bit for bit, Jp and Jd included.  NaN
+ * operands: as convertToDual above (which NaN payload a sum propagates is the
+ * hardware's choice; positions and every non-NaN bit agree).
+ *
+ * Shapes of the one-workgroup step (kind 2): N or M above 32, M < 64,
+ * nd <= 64, ns <= 64, N <= 192, and (N, M) one that the batched path 3
+ * (pqp_batch_solve_path(N, M) == 3 at default tuning) solves within one
+ * workgroup's LDS with the plant step's own words added -- 140 x 35 and
+ * 40 x 12 among them.  Converge mode only.
+ * -------------------------------------------------------------------- */
+
+/* 0: (N, M, nd, ns) is no shape pqp_plant_step runs; 1: the one-wave step of 2f
+ * (pqp_plant_supported); 2: the one-workgroup step.  No error set. */
+int pqp_plant_kind(int N, int M, int nd, int ns);
+
+/* pqp_plant_create's arguments and derivations (Qp, Gp Qp_inv, Qd, Theta, by the same
+ * launchers: the same bits), for a shape of kind 1 or 2; for kind 2 it also finds, once,
+ * whether Qd is bit-symmetric and whether it holds a NaN or an inf (which forms of the
+ * sums the step may take; no bit depends on them).  Kind 0: PQP_ERR_ARG, *out NULL, the
+ * limits in the message. */
+int pqp_plant_create_horizon(int device, int N, int M, int nd, int ns, const float *Qp_inv, const float *Gp,
+                             const float *Kp, const float *Fp1, const float *Fp2, const float *Fp3,
+                             const float *Mp1, const float *Mp2, const float *Mp3, const float *Mp4,
+                             const float *Mp5, const float *Mp6, pqp_plant **out);
+
 #ifdef __cplusplus
 }
 #endif

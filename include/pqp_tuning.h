@@ -116,7 +116,8 @@ extern "C" {
  *                          resident wave slot), so that a small batch walks the
  *                          kernel's state loop (tests)
  *   plant_pipe [0]         pqp_plant_step's iteration: 0 plain, 1 software-pipelined
- *                          (k_solve_wave's two forms)
+ *                          (k_solve_wave's two forms); ignored by the one-workgroup
+ *                          step of pqp.h 2g
  *  Paths and failure tests:
  *   persist_off [0]        fixed mode of n_dual <= 1024 through the graph-replayed
  *                          relay instead of the persistent launch
@@ -150,7 +151,10 @@ int pqp_tune(const char *key, long long value, long long *old_value);
  *                      pqp_batch_solve launch (the batch_chunk knob if set)
  *   plant_slots        in: *value = N | M << 8 | nd << 16 | ns << 24 | pipe << 32;
  *                      out: workgroups of pqp_plant_step resident at once on the
- *                      current device (CUs x occupancy): its grid is min(B, that) */
+ *                      current device (CUs x occupancy): its grid is min(B, that)
+ *                      (the one-wave step's shapes, pqp_plant_kind 1)
+ *   plant_mid_lds      in: *value = N << 32 | M; out: bytes of LDS one workgroup of the
+ *                      one-workgroup plant step (pqp.h 2g) takes; host only */
 int pqp_tune_get(const char *key, long long *value);
 
 /* Record an on-device timeline (s_memrealtime / s_memtime marks) of the

@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <memory>
 #include <mutex>
 #include <thread>
@@ -415,8 +416,10 @@ struct pqp_rowblock {
 // Immutable after create; a step writes only the caller's buffers.
 struct pqp_plant {
     int N = 0, M = 0, nd = 0, ns = 0;
+    int kind = 1;            // pqp_plant_kind: 1 the one-wave step, 2 the one-workgroup step (2g)
     int dev = -1;            // the device it was made on (its steps run there)
-    int slots[2] = {0, 0};   // workgroups resident at once: [0] the plain form, [1] the pipelined one
+    int slots[2] = {0, 0};   // workgroups resident at once: [0] the plain form, [1] the pipelined one (kind 2: both its one form)
+    pqp::PlantMidFlags mid{};  // kind 2: what Qd alone decides in k_solve_mid2's staging
     pqp::DevBuf Qinv, Gp, Kp, Qp, Qd, GQ, theta;
     pqp::DevBuf Fp1, Fp2, Fp3, Mp1, Mp2, Mp3, Mp4, Mp5, Mp6;
     pqp::PlantData data{};
@@ -1136,7 +1139,7 @@ using namespace pqp;
 
 extern "C" {
 
-int pqp_version(void) { return 108; }  // ABI revision: INTEGRATION.md section 6
+int pqp_version(void) { return 109; }  // ABI revision: INTEGRATION.md section 6
 
 // ---------------------------------------------------------------------------
 // 2a. status-returning host API
@@ -1967,27 +1970,43 @@ int pqp_batch_solve(int B, int N, int M, const float* d_Qd, const float* d_Fd, c
 // ---------------------------------------------------------------------------
 int pqp_plant_supported(int N, int M, int nd, int ns) { return plant_shape_ok(N, M, nd, ns) ? 1 : 0; }
 
-int pqp_plant_create(int device, int N, int M, int nd, int ns, const float* Qp_inv, const float* Gp, const float* Kp,
-                     const float* Fp1, const float* Fp2, const float* Fp3, const float* Mp1, const float* Mp2,
-                     const float* Mp3, const float* Mp4, const float* Mp5, const float* Mp6, pqp_plant** out) {
-    if (!out) return set_error(PQP_ERR_ARG, "pqp_plant_create: null handle pointer");
+// 2g: 0 unsupported, 1 the one-wave step (2f), 2 the one-workgroup step at horizon sizes
+int pqp_plant_kind(int N, int M, int nd, int ns) {
+    if (plant_shape_ok(N, M, nd, ns)) return 1;
+    return plant_mid_shape_ok(N, M, nd, ns) ? 2 : 0;
+}
+
+// pqp_plant_create (kind 1 only) and pqp_plant_create_horizon (kinds 1 and 2): `fn` names the caller in messages
+static int plant_create(const char* fn, bool horizon, int device, int N, int M, int nd, int ns, const float* Qp_inv,
+                        const float* Gp, const float* Kp, const float* Fp1, const float* Fp2, const float* Fp3,
+                        const float* Mp1, const float* Mp2, const float* Mp3, const float* Mp4, const float* Mp5,
+                        const float* Mp6, pqp_plant** out) {
+    if (!out) return set_error(PQP_ERR_ARG, "%s: null handle pointer", fn);
     *out = nullptr;
-    if (!plant_shape_ok(N, M, nd, ns))
+    const int kind = pqp_plant_kind(N, M, nd, ns);
+    if (!horizon && kind != 1)
         return set_error(PQP_ERR_ARG, "pqp_plant_create: (N=%d, M=%d, nd=%d, ns=%d) is not a shape pqp_plant_step runs "
                                       "(N <= 32, M <= 32, N + M < 64, nd <= 64, ns <= 64): use ProblemBatch "
                                       "(pqp_batch_*) for it", N, M, nd, ns);
+    if (kind == 0)
+        return set_error(PQP_ERR_ARG, "%s: (N=%d, M=%d, nd=%d, ns=%d) is not a shape pqp_plant_step runs (one wave: "
+                                      "N <= 32, M <= 32, N + M < 64; one workgroup: M < 64, N <= 192 and the plant "
+                                      "within %zu bytes of LDS, which (N, M) takes %zu of; nd <= 64, ns <= 64): use "
+                                      "ProblemBatch (pqp_batch_*) for it", fn, N, M, nd, ns, kLdsBudget,
+                         (N > 0 && M > 0 && N < (1 << 14) && M < (1 << 14)) ? plant_mid_lds_bytes(N, M) : (size_t)0);
     if (!Qp_inv || !Gp || !Kp || !Fp1 || !Fp2 || !Fp3 || !Mp1 || !Mp2 || !Mp3 || !Mp4 || !Mp5 || !Mp6)
-        return set_error(PQP_ERR_ARG, "pqp_plant_create: null input");
+        return set_error(PQP_ERR_ARG, "%s: null input", fn);
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return set_error(PQP_ERR_NO_DEVICE, "libpqp: no HIP device visible");
     if (device < 0 && hipGetDevice(&device) != hipSuccess)
         return set_error(PQP_ERR_NO_DEVICE, "libpqp: cannot query the current device");
-    if (device >= n) return set_error(PQP_ERR_ARG, "pqp_plant_create: device %d of %d", device, n);
+    if (device >= n) return set_error(PQP_ERR_ARG, "%s: device %d of %d", fn, device, n);
     DeviceGuard on(device);
     PQP_TRY(ensure_device());
     hipStream_t s = lib_stream();
     std::unique_ptr<pqp_plant> P(new pqp_plant());
     P->N = N, P->M = M, P->nd = nd, P->ns = ns;
+    P->kind = kind;
     P->dev = device;
     PQP_TRY(upload(P->Qinv, Qp_inv, (size_t)M * M, s));
     PQP_TRY(upload(P->Gp, Gp, (size_t)N * M, s));
@@ -2015,12 +2034,32 @@ int pqp_plant_create(int device, int N, int M, int nd, int ns, const float* Qp_i
     PQP_HIP(launch_matmul_seq_b(1, P->Qd.f(), P->GQ.f(), 0, P->Gp.f(), 1, N, M, N, nm, nm, nn, s));        // Qd :440-455
     PQP_HIP(launch_theta_rows(P->Qd.f(), N, N, N, P->theta.f(), s));                                       // Theta :503-519
     for (int pipe = 0; pipe < 2; ++pipe) {
-        P->slots[pipe] = plant_resident_wgs(N, M, nd, ns, pipe != 0);
+        P->slots[pipe] = kind == 2 ? plant_mid_resident_wgs(N, M) : plant_resident_wgs(N, M, nd, ns, pipe != 0);
         if (P->slots[pipe] <= 0) {
             const hipError_t e = hipGetLastError();
-            return set_error(PQP_ERR_HIP, "pqp_plant_create: no occupancy for (N=%d, M=%d, nd=%d, ns=%d): %s", N, M, nd,
-                             ns, hipGetErrorString(e));
+            return set_error(PQP_ERR_HIP, "%s: no occupancy for (N=%d, M=%d, nd=%d, ns=%d): %s", fn, N, M, nd, ns,
+                             hipGetErrorString(e));
         }
+    }
+    if (kind == 2) {
+        // what k_solve_mid2 finds in Qd when it stages a problem, once: bit symmetry by the batched
+        // entry points' kernel, NaN / inf by a scan of the host copy
+        DevBuf symd;
+        PQP_TRY(symd.alloc(sizeof(int)));
+        PQP_HIP(launch_check_symmetric(1, P->Qd.f(), N, static_cast<int*>(symd.p), s));
+        int hsym = 0;
+        PQP_HIP(hipMemcpyAsync(&hsym, symd.p, sizeof(int), hipMemcpyDeviceToHost, s));
+        std::vector<float> hq((size_t)N * N);
+        PQP_TRY(download(hq.data(), P->Qd.p, hq.size(), s));
+        PQP_HIP(hipStreamSynchronize(s));
+        bool nan = false, inf = false;
+        for (float q : hq) {
+            nan = nan || q != q;
+            inf = inf || std::fabs(q) == std::numeric_limits<float>::infinity();
+        }
+        P->mid.sym = hsym != 0 ? 1 : 0;
+        P->mid.fast = nan ? 0 : 1;
+        P->mid.qfinite = (!nan && !inf) ? 1 : 0;
     }
     PQP_HIP(hipStreamSynchronize(s));  // the host arrays and the Gauss_Jordan scratch are free after it
     PlantData& d = P->data;
@@ -2032,6 +2071,21 @@ int pqp_plant_create(int device, int N, int M, int nd, int ns, const float* Qp_i
     d.Mp4 = P->Mp4.f(), d.Mp5 = P->Mp5.f(), d.Mp6 = P->Mp6.f();
     *out = P.release();
     return PQP_OK;
+}
+
+int pqp_plant_create(int device, int N, int M, int nd, int ns, const float* Qp_inv, const float* Gp, const float* Kp,
+                     const float* Fp1, const float* Fp2, const float* Fp3, const float* Mp1, const float* Mp2,
+                     const float* Mp3, const float* Mp4, const float* Mp5, const float* Mp6, pqp_plant** out) {
+    return plant_create("pqp_plant_create", false, device, N, M, nd, ns, Qp_inv, Gp, Kp, Fp1, Fp2, Fp3, Mp1, Mp2, Mp3,
+                        Mp4, Mp5, Mp6, out);
+}
+
+int pqp_plant_create_horizon(int device, int N, int M, int nd, int ns, const float* Qp_inv, const float* Gp,
+                             const float* Kp, const float* Fp1, const float* Fp2, const float* Fp3, const float* Mp1,
+                             const float* Mp2, const float* Mp3, const float* Mp4, const float* Mp5, const float* Mp6,
+                             pqp_plant** out) {
+    return plant_create("pqp_plant_create_horizon", true, device, N, M, nd, ns, Qp_inv, Gp, Kp, Fp1, Fp2, Fp3, Mp1, Mp2,
+                        Mp3, Mp4, Mp5, Mp6, out);
 }
 
 int pqp_plant_destroy(pqp_plant* p) {
@@ -2077,6 +2131,12 @@ int pqp_plant_step(pqp_plant* p, int B, const float* d_x, const float* d_D, cons
     S.Fp = d_Fp, S.Mp = d_Mp, S.Fd = d_Fd, S.Md = d_Md, S.Jp = d_Jp, S.Jd = d_Jd;
     const bool pipe = g_plant_pipe != 0;
     DeviceGuard on(p->dev);
+    if (p->kind == 2) {  // the one-workgroup step: plant_pipe has no meaning for it
+        PlantMidFlags F = p->mid;
+        F.dense = g_tune.mid2_dense ? 1 : 0;
+        PQP_HIP(launch_plant_step_mid(p->data, S, F, p->slots[0], static_cast<hipStream_t>(stream)));
+        return PQP_OK;
+    }
     PQP_HIP(launch_plant_step(p->data, S, p->slots[pipe ? 1 : 0], pipe, static_cast<hipStream_t>(stream)));
     return PQP_OK;
 }
@@ -2461,6 +2521,13 @@ extern "C" int pqp_tune_get(const char* key, long long* value) {
         if (!pqp::plant_shape_ok(N, M, nd, ns)) return pqp::set_error(PQP_ERR_ARG, "pqp_tune_get: plant_slots of an unsupported shape");
         PQP_TRY(pqp::ensure_device());
         *value = pqp::plant_resident_wgs(N, M, nd, ns, (v >> 32 & 1) != 0);
+        return PQP_OK;
+    }
+    if (std::strcmp(key, "plant_mid_lds") == 0) {  // in: N << 32 | M; out: bytes of LDS of the one-workgroup plant step (host only)
+        const long long v = *value;
+        const int N = (int)(v >> 32), M = (int)(v & 0xffffffff);
+        if (N < 1 || M < 1 || N > 4096 || M > 4096) return pqp::set_error(PQP_ERR_ARG, "pqp_tune_get: plant_mid_lds of N=%d, M=%d", N, M);
+        *value = (long long)pqp::plant_mid_lds_bytes(N, M);
         return PQP_OK;
     }
     if (std::strcmp(key, "converge_grid") == 0) {  // in: N << 32 | M

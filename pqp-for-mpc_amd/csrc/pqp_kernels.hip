@@ -5867,3 +5867,5 @@ hipError_t launch_extract_state(int B, const SolveState* st, long long* h, int* 
 #include "pqp_relin.hip"
 // So does the resident-plant control step (k_plant_step).
 #include "pqp_plant.hip"
+// ... and its one-workgroup form at horizon sizes (k_plant_step_mid), which calls k_solve_mid2's helpers above.
+#include "pqp_plant_mid.hip"

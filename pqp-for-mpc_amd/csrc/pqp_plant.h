@@ -46,4 +46,25 @@ int plant_resident_wgs(int N, int M, int nd, int ns, bool pipe);
 // synchronisation.  slots: plant_resident_wgs' count for the form launched.
 hipError_t launch_plant_step(const PlantData& P, const PlantStep& S, int slots, bool pipe, hipStream_t s);
 
+// ---- the one-workgroup step at horizon sizes (pqp_plant_mid.hip, pqp.h 2g) ----
+// What k_solve_mid2 derives from Qd alone when it stages a problem, found once
+// at create: sym -- Qd bit-symmetric (Y'Qd's column j read as row j); fast -- no
+// NaN in Qd (the v_max / v_med3 splits); qfinite -- fast and no inf (the
+// product-first update).  dense: the tuning knob mid2_dense (sum every k).
+struct PlantMidFlags {
+    int sym, fast, qfinite, dense;
+};
+// The shapes k_plant_step_mid runs: those the batched path 3 solves on the
+// converge-mode k_solve_mid2 at default knobs (M < 64, at most 16 waves, the
+// staged matrices within one workgroup's LDS), N or M above 32, nd, ns <= 64.
+bool plant_mid_shape_ok(int N, int M, int nd, int ns);
+// bytes of LDS one workgroup of the step takes (mid2_layout and the prologue's words)
+size_t plant_mid_lds_bytes(int N, int M);
+// Workgroups resident on the current device at once; 0 with the error left in
+// hipGetLastError.  Queried once per plant, never in a step.
+int plant_mid_resident_wgs(int N, int M);
+// ONE launch: states b = w, w + grid, ... on workgroup w; no allocation, no synchronisation.
+hipError_t launch_plant_step_mid(const PlantData& P, const PlantStep& S, const PlantMidFlags& F, int slots,
+                                 hipStream_t s);
+
 }  // namespace pqp

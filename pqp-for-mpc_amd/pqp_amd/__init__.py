@@ -105,6 +105,8 @@ SIGNATURES = {
                              + [_vp] * 4 + [_vp, _vp]),
     "pqp_plant_supported": (C.c_int, [C.c_int] * 4),
     "pqp_plant_create": (C.c_int, [C.c_int] * 5 + [_fp] * 12 + [C.POINTER(C.c_void_p)]),
+    "pqp_plant_kind": (C.c_int, [C.c_int] * 4),
+    "pqp_plant_create_horizon": (C.c_int, [C.c_int] * 5 + [_fp] * 12 + [C.POINTER(C.c_void_p)]),
     "pqp_plant_destroy": (C.c_int, [_vp]),
     "pqp_plant_get": (C.c_int, [_vp, _fp, _fp, _fp]),
     "pqp_plant_max_updates": (C.c_longlong, [_vp]),
@@ -867,6 +869,11 @@ class Plant:
     N + M < 64, nd, ns <= 64 (``Plant.supported``); others raise with the
     library's message -- use :class:`ProblemBatch` for them.
 
+    ``horizon=True`` (section 2g, pqp_plant_create_horizon) also takes the
+    shapes of a horizon of stages -- M < 64, N up to what one workgroup's LDS
+    holds (``Plant.kind`` gives 2 for them; 140 x 35 among them) -- which run
+    one workgroup per state at a time, in one launch and with the same bits.
+
     ``arrays``: Qp_inv, Gp, Kp, Fp1, Fp2, Fp3, Mp1 ... Mp6 in the reference's
     layouts (read_example's), and optionally D (the disturbance ``step`` uses
     when it is given none)."""
@@ -874,7 +881,7 @@ class Plant:
     PLANT = ("Qp_inv", "Gp", "Kp", "Fp1", "Fp2", "Fp3", "Mp1", "Mp2", "Mp3", "Mp4", "Mp5", "Mp6")
     OUT = ("Y", "U", "h", "status", "Fp", "Mp", "Fd", "Md", "Jp", "Jd")
 
-    def __init__(self, N: int, M: int, nd: int, ns: int, device=None, **arrays):
+    def __init__(self, N: int, M: int, nd: int, ns: int, device=None, horizon: bool = False, **arrays):
         import torch
 
         self.torch = torch
@@ -888,14 +895,15 @@ class Plant:
             if k not in arrays:
                 raise ValueError(f"Plant: missing array {k}")
             host[k] = _f32(arrays[k]).reshape(-1)
-            if host[k].size != sizes[k] and lib().pqp_plant_supported(self.N, self.M, self.nd, self.ns):
+            ok = lib().pqp_plant_kind if horizon else lib().pqp_plant_supported
+            if host[k].size != sizes[k] and ok(self.N, self.M, self.nd, self.ns):
                 raise ValueError(f"Plant: {k} has {host[k].size} values, not {sizes[k]}")
         self._D = _f32(arrays["D"]).reshape(-1) if arrays.get("D") is not None else None
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         h = C.c_void_p()
         dev = self.device.index if self.device.index is not None else -1
-        _check(lib().pqp_plant_create(dev, self.N, self.M, self.nd, self.ns, *[_buf(host[k]) for k in self.PLANT],
-                                      C.byref(h)))
+        create = lib().pqp_plant_create_horizon if horizon else lib().pqp_plant_create
+        _check(create(dev, self.N, self.M, self.nd, self.ns, *[_buf(host[k]) for k in self.PLANT], C.byref(h)))
         self._h = h
         self.max_updates = int(lib().pqp_plant_max_updates(h))
         self._Dt = None
@@ -903,6 +911,12 @@ class Plant:
     @staticmethod
     def supported(N: int, M: int, nd: int, ns: int) -> bool:
         return bool(lib().pqp_plant_supported(int(N), int(M), int(nd), int(ns)))
+
+    @staticmethod
+    def kind(N: int, M: int, nd: int, ns: int) -> int:
+        """0: not a plant shape; 1: the one-wave step (``supported``); 2: the
+        one-workgroup step, which ``horizon=True`` opts into."""
+        return int(lib().pqp_plant_kind(int(N), int(M), int(nd), int(ns)))
 
     @classmethod
     def from_example(cls, directory, device=None) -> "Plant":
@@ -1122,6 +1136,61 @@ def horizon_batch(directory, H: int, states, device=None) -> ProblemBatch:
     torch.cuda.current_stream(dev).synchronize()  # the staging tensors go out of scope
     pb.gauss_jordan().convert_to_dual()
     return pb
+
+
+def horizon_plant(directory, H: int) -> dict:
+    """H stacked stages of the bundled plant (example/*.txt) as ONE plant with
+    one state vector, for ``Plant(..., horizon=True)``: Fp1, Fp2, Fp3 of the
+    stages stacked, Qp_inv and Gp block-diagonal as ``horizon_batch`` places
+    them, Kp stacked, Mp1 ... Mp6 the bundled plant's.  N = 28 H, M = 7 H,
+    nd = 1, ns = 29.  -> dict(N, M, nd, ns, D, x and Plant.PLANT's arrays); numpy only."""
+    E = read_example(directory)
+    H = int(H)
+    n, m, nd, ns = E["N"], E["M"], E["nd"], E["ns"]
+    A = dict(N=n * H, M=m * H, nd=nd, ns=ns, D=_f32(E["D"]).reshape(-1), x=_f32(E["x"]).reshape(-1))
+    QI, GP = np.zeros((H * m, H * m), np.float32), np.zeros((H * n, H * m), np.float32)
+    for h in range(H):  # the diagonal blocks (the rest stays +0.0)
+        QI[h * m:(h + 1) * m, h * m:(h + 1) * m] = _f32(E["Qp_inv"]).reshape(m, m)
+        GP[h * n:(h + 1) * n, h * m:(h + 1) * m] = _f32(E["Gp"]).reshape(n, m)
+    A.update(Qp_inv=QI.reshape(-1), Gp=GP.reshape(-1), Kp=np.tile(_f32(E["Kp"]).reshape(-1), H))
+    for k in ("Fp1", "Fp2", "Fp3"):
+        A[k] = np.tile(_f32(E[k]).reshape(-1), H)  # row-major [m, .] blocks one under the other
+    for k in ("Mp1", "Mp2", "Mp3", "Mp4", "Mp5", "Mp6"):
+        A[k] = _f32(E[k]).reshape(-1)
+    return A
+
+
+def plant_batch(A: dict, N: int, M: int, nd: int, ns: int, x, D, device=None) -> ProblemBatch:
+    """The batched route for ONE plant at B states -- what ``Plant.step`` is
+    pinned to: a ProblemBatch whose every problem holds the plant's Qp_inv, Gp
+    and Kp (``A``: Plant.PLANT's arrays), Fp / Mp from x [B, ns] and D [B, nd]
+    (pqp_batch_compute_fp / _mp), Qp and the duals built on the device.
+    ``plant_restate`` moves it to new states."""
+    import torch
+
+    x = np.ascontiguousarray(np.asarray(x.cpu() if torch.is_tensor(x) else x, np.float32)).reshape(-1, ns)
+    pb = ProblemBatch(x.shape[0], N, M, device)
+    T = lambda a: torch.as_tensor(np.asarray(a, np.float32).reshape(-1), device=pb.device).contiguous()  # noqa: E731
+    for k in ("Qp_inv", "Gp", "Kp"):
+        getattr(pb, k).copy_(T(A[k]).reshape(1, -1).expand(pb.B, -1))
+    pb._plant_any = (dict(M=M, nd=nd, ns=ns), {k: T(A[k]) for k in ("Fp1", "Fp2", "Fp3", "Mp1", "Mp2", "Mp3", "Mp4",
+                                                                    "Mp5", "Mp6")})
+    _plant_terms(pb, x, D)
+    return pb.gauss_jordan().convert_to_dual()
+
+
+def _plant_terms(pb, x, D):
+    torch = pb.torch
+    E, plant = pb._plant_any
+    dev = lambda a, c: torch.as_tensor(a if torch.is_tensor(a) else np.asarray(a, np.float32), dtype=torch.float32,  # noqa: E731
+                                       device=pb.device).reshape(pb.B, c).contiguous()
+    _mpc_linear_terms(pb, E, plant, dev(D, E["nd"]), dev(x, E["ns"]))  # synchronous
+
+
+def plant_restate(pb: ProblemBatch, x, D) -> ProblemBatch:
+    """``plant_batch``'s problems at new states: Fp, Mp, then Fd, Md in place (``mpc_restate`` for any plant)."""
+    _plant_terms(pb, x, D)
+    return pb.relinearize()
 
 
 class RowBlock:
