@@ -261,6 +261,35 @@ int pqp_batch_iterate_sym(int B, int N, const float *d_QdT, int ldq, long long q
                           const float *d_Fd, int ldv, const float *d_Y0, float *d_Y, int updates, void *stream);
 
 /* ----------------------------------------------------------------------
+ * 2b'. B states of ONE dual problem: Qd and theta shared, Fd and Y per state
+ * (the MPC workload: one plant at B states).  One Qd is read once per
+ * pqp_batch_shared_states states instead of once per state, and it stays in
+ * cache: no [B][N][ldq] copies, no HBM stream (k_batch_shared).
+ * -------------------------------------------------------------------- */
+
+/* States per workgroup the shared update uses for this shape; 0 when the shape is
+ * not supported (no error set).  Depends on (N, ldq) only: 16 up to ldq = 1280,
+ * 8 up to ldq = 2560 (two LDS images of the states' iterates, 160 KiB), else 0. */
+int pqp_batch_shared_states(int N, int ldq);
+
+/* pqp_batch_iterate for B states of ONE dual problem: d_QdT [N][ldq] and d_theta [N]
+ * are one problem's (2b's layout with B = 1: ldq >= N, ldq % 4 == 0, 16-byte aligned);
+ * d_Fd, d_Y0, d_Y are [B][ldv], ldv >= N.  State b gets, bit for bit, what
+ * pqp_batch_iterate gives problem b of a batch whose every problem holds this Qd and
+ * theta.  d_Y0 NULL (Y = 1000), a separate buffer, or d_Y itself.  updates >= 0
+ * (0 copies Y0, or 1000, to Y).  One launch (per 256 updates, as pqp_batch_iterate),
+ * asynchronous on `stream`, no allocation, no synchronisation.  Qd need not be
+ * symmetric.  Padding as in 2b: rows N..ldq-1 of each column and the vector tails
+ * [N, ldv) are never read into a result and never written.  NaN operands: the
+ * output is NaN wherever pqp_batch_iterate's is (sign and payload may differ) and
+ * every non-NaN output is bit-identical.  Argument errors give PQP_ERR_ARG before
+ * any device is looked for; a shape with pqp_batch_shared_states(N, ldq) == 0 is
+ * one of them. */
+int pqp_batch_iterate_shared(int B, int N, const float *d_QdT, int ldq, const float *d_theta,
+                             const float *d_Fd, int ldv, const float *d_Y0, float *d_Y,
+                             int updates, void *stream);
+
+/* ----------------------------------------------------------------------
  * 2c. Batched small problems: many independent MPC problems (batched
  * horizons / states), one workgroup each.  Every array holds B problems back
  * to back in the reference's row-major layout (e.g. Qd is [B][N*N], Kp is

@@ -22,6 +22,7 @@
 #include "pqp_launch.h"
 #include "pqp_plant.h"
 #include "pqp_relin.h"
+#include "pqp_shared.h"
 
 namespace pqp {
 
@@ -1139,7 +1140,7 @@ using namespace pqp;
 
 extern "C" {
 
-int pqp_version(void) { return 109; }  // ABI revision: INTEGRATION.md section 6
+int pqp_version(void) { return 110; }  // ABI revision: INTEGRATION.md section 6
 
 // ---------------------------------------------------------------------------
 // 2a. status-returning host API
@@ -1511,6 +1512,28 @@ int pqp_batch_iterate_sym(int B, int N, const float* d_QdT, int ldq, long long q
         return set_error(PQP_ERR_ARG, "pqp_batch_iterate_sym: ldq=%d needs more than 160 KiB of LDS", ldq);
     PQP_HIP(launch_batch_iterate_sym(B, d_QdT, qstride, ldq, N, d_theta, d_Fd, ldv, d_Y0, d_Y, updates,
                                      static_cast<hipStream_t>(stream)));
+    return PQP_OK;
+}
+
+// B states of one problem (pqp.h 2b'): k_batch_shared
+int pqp_batch_shared_states(int N, int ldq) { return pqp::batch_shared_states(N, ldq); }
+
+int pqp_batch_iterate_shared(int B, int N, const float* d_QdT, int ldq, const float* d_theta, const float* d_Fd,
+                             int ldv, const float* d_Y0, float* d_Y, int updates, void* stream) {
+    // check_batch's rules for one problem's QdT, and this entry point's own, before any device is looked for
+    if (B <= 0 || N <= 0) return set_error(PQP_ERR_ARG, "B and N must be positive (B=%d, N=%d)", B, N);
+    if (!d_QdT || (reinterpret_cast<uintptr_t>(d_QdT) & 15))
+        return set_error(PQP_ERR_ARG, "QdT must be a 16-byte aligned device pointer");
+    if (ldq < N || (ldq & 3)) return set_error(PQP_ERR_ARG, "ldq (%d) must be >= N (%d) and a multiple of 4", ldq, N);
+    if (ldv < N) return set_error(PQP_ERR_ARG, "ldv (%d) must be >= N (%d)", ldv, N);
+    if (updates < 0) return set_error(PQP_ERR_ARG, "pqp_batch_iterate_shared: updates (%d) must be >= 0", updates);
+    if (!d_theta || !d_Fd || !d_Y) return set_error(PQP_ERR_ARG, "pqp_batch_iterate_shared: null pointer");
+    if (pqp::batch_shared_states(N, ldq) == 0)
+        return set_error(PQP_ERR_ARG, "pqp_batch_iterate_shared: ldq=%d is not supported: 8 states need 64*ldq bytes "
+                                      "of LDS, the limit is 160 KiB (ldq <= 2560)", ldq);
+    PQP_TRY(ensure_device());
+    PQP_HIP(launch_batch_shared(B, d_QdT, ldq, N, d_theta, d_Fd, ldv, d_Y0, d_Y, updates,
+                                static_cast<hipStream_t>(stream)));
     return PQP_OK;
 }
 

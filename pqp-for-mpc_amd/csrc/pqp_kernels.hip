@@ -5869,3 +5869,5 @@ hipError_t launch_extract_state(int B, const SolveState* st, long long* h, int* 
 #include "pqp_plant.hip"
 // ... and its one-workgroup form at horizon sizes (k_plant_step_mid), which calls k_solve_mid2's helpers above.
 #include "pqp_plant_mid.hip"
+// The shared-Qd batched update (k_batch_shared): B states of one dual problem.
+#include "pqp_shared.hip"

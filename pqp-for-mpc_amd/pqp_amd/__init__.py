@@ -91,6 +91,8 @@ SIGNATURES = {
     "pqp_batch_solve_kernel": (C.c_int, [C.c_int, C.c_int]),
     "pqp_batch_iterate_sym": (C.c_int, [C.c_int, C.c_int, _vp, C.c_int, C.c_longlong, _vp, _vp, C.c_int, _vp, _vp,
                                         C.c_int, _vp]),
+    "pqp_batch_shared_states": (C.c_int, [C.c_int, C.c_int]),
+    "pqp_batch_iterate_shared": (C.c_int, [C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp]),
     "pqp_batch_symmetric": (C.c_int, [C.c_int, C.c_int, _vp, C.c_int, C.c_longlong, _vp, C.POINTER(C.c_int), _vp]),
     "pqp_batch_prepare": (C.c_int, [C.c_int] * 3 + [_vp] * 8 + [C.POINTER(C.c_int), _vp]),
     "pqp_batch_solve_prepared": (C.c_int, [C.c_int] * 3 + [_vp] * 14 + [C.c_int, C.c_longlong, C.c_longlong]
@@ -662,6 +664,70 @@ class Batch:
         """Problem b's Qd back in the reference's row-major layout (host)."""
         qt = self.QdT[b * self.qstride:b * self.qstride + self.N * self.ldq].reshape(self.N, self.ldq)[:, : self.N]
         return qt.t().contiguous().cpu().numpy().reshape(-1)
+
+
+class SharedBatch:
+    """B states of ONE dual problem of size N resident in HBM: QdT is one
+    problem's [N][ldq] (column-major, as in Batch) and theta one [ldv] vector;
+    Fd and Y are [B][ldv].  iterate() runs pqp_batch_iterate_shared, which
+    gives state b what Batch.iterate() gives problem b of a batch holding B
+    copies of this Qd, bit for bit, without the copies.  All launches go to
+    torch's current HIP stream of ``device``."""
+
+    def __init__(self, B: int, N: int, device=None, ldq: int | None = None, ldv: int | None = None):
+        import torch
+
+        self.torch = torch
+        self.B, self.N = int(B), int(N)
+        self.ldq = int(ldq) if ldq else round_up(self.N, 4)
+        self.ldv = int(ldv) if ldv else round_up(self.N, 4)
+        self.states = int(lib().pqp_batch_shared_states(self.N, self.ldq))  # per workgroup; 0: unsupported shape
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        kw = dict(dtype=torch.float32, device=self.device)
+        self.QdT = torch.zeros(self.N * self.ldq, **kw)
+        self.theta = torch.zeros(self.ldv, **kw)
+        self.Fd = torch.zeros(self.B, self.ldv, **kw)
+        self.Y = torch.zeros(self.B, self.ldv, **kw)
+        self.Y2 = torch.zeros(self.B, self.ldv, **kw)
+
+    def _stream(self):
+        return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
+
+    _p = staticmethod(Batch._p)
+
+    def load(self, Qd, Fd):
+        """Load one row-major Qd (N*N or [N][N]) and the states' Fd ([B][N])
+        given as numpy/torch; packs Qd to QdT on the GPU and computes theta."""
+        torch = self.torch
+        Qd = torch.as_tensor(np.asarray(Qd, np.float32) if not torch.is_tensor(Qd) else Qd, dtype=torch.float32)
+        Qd = Qd.reshape(self.N * self.N).to(self.device).contiguous()
+        Fd = torch.as_tensor(np.asarray(Fd, np.float32) if not torch.is_tensor(Fd) else Fd, dtype=torch.float32)
+        self.Fd.zero_()
+        self.Fd[:, : self.N] = Fd.reshape(self.B, self.N).to(self.device)
+        self.QdT.zero_()
+        _check(lib().pqp_batch_pack(1, self.N, self._p(Qd), self._p(self.QdT), self.ldq, self.N * self.ldq,
+                                    self._stream()))
+        _check(lib().pqp_batch_theta(1, self.N, self._p(self.QdT), self.ldq, self.N * self.ldq, self._p(self.theta),
+                                     self.ldv, self._stream()))
+        torch.cuda.current_stream(self.device).synchronize()  # the Qd staging buffer goes out of scope
+        return self
+
+    def reset(self, value: float = 1000.0):
+        self.Y.fill_(value)
+        return self
+
+    def iterate(self, updates: int, from_start: bool = True):
+        """`updates` fused updates per state in one launch (pqp_batch_iterate_shared);
+        from_start=True begins at the reference's Y = 1000."""
+        y0 = None if from_start else self._p(self.Y)
+        _check(lib().pqp_batch_iterate_shared(self.B, self.N, self._p(self.QdT), self.ldq, self._p(self.theta),
+                                              self._p(self.Fd), self.ldv, y0, self._p(self.Y2), int(updates),
+                                              self._stream()))
+        self.Y, self.Y2 = self.Y2, self.Y
+        return self
+
+    def result(self) -> np.ndarray:
+        return self.Y[:, : self.N].cpu().numpy()
 
 
 class ProblemBatch:
