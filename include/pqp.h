@@ -253,8 +253,11 @@ int pqp_batch_symmetric(int B, int N, const float *d_QdT, int ldq, long long qst
  * pqp_batch_generate and for convertToDual with a diagonal Qp_inv).  Same
  * arguments, same d_Y0 rules (NULL, a separate buffer, or d_Y itself), same
  * bits.  At N == ldq == 1024 each 64 x 64 tile of Qd is read from HBM once
- * for itself and its mirror (k_batch_half); other shapes, and the tuning knob
- * iterate_half = 0, forward to pqp_batch_iterate.  With a Qd that is not
+ * for itself and its mirror (k_batch_half; a tile off the diagonal is summed
+ * in a cheaper form while its entries and the iterate's entries it meets are
+ * finite and the latter non-negative, which the kernel tests itself: the bits
+ * do not depend on it); other shapes, and the tuning knob iterate_half = 0,
+ * forward to pqp_batch_iterate.  With a Qd that is not
  * symmetric the result is that of the matrix whose upper triangle mirrors the
  * stored lower one in some tiles: wrong, but nothing is read out of bounds. */
 int pqp_batch_iterate_sym(int B, int N, const float *d_QdT, int ldq, long long qstride, const float *d_theta,

@@ -110,8 +110,12 @@ extern "C" {
  *                          k_batch_iterate), 1 k_batch_iterate, 2 k_batch_stream,
  *                          3 k_batch_resident without the register blocks
  *   iterate_half [1]       pqp_batch_iterate_sym: 1 k_batch_half where the shape
- *                          fits (n_dual 1024), 0 forward to pqp_batch_iterate
- *                          (in-process A/B of the two; same bits)
+ *                          fits (n_dual 1024), off-diagonal tiles in the
+ *                          product-first form while the tile and the iterate's
+ *                          k-block are finite (decided in the kernel), 2
+ *                          k_batch_half with the lean form only, 0 forward to
+ *                          pqp_batch_iterate (in-process A/B; same bits); other
+ *                          values are taken as 1
  *   plant_grid [0]         pqp_plant_step: at most this many workgroups (0: every
  *                          resident wave slot), so that a small batch walks the
  *                          kernel's state loop (tests)

@@ -2507,6 +2507,8 @@ extern "C" int pqp_tune(const char* key, long long value, long long* old_value) 
         value = value > 0 ? value : (1 << 16);
     } else if (std::strcmp(key, "persist_stall_wg") == 0) {
         value = value >= 0 ? value : -1;
+    } else if (std::strcmp(key, "iterate_half") == 0) {
+        value = (value >= 0 && value <= 2) ? value : 1;  // 0 forward, 1 product-first, 2 lean only
     }
     if (k->i) *k->i = (int)value;
     else if (k->b) *k->b = value != 0;

@@ -15,7 +15,8 @@
 // the arithmetic, and tests/halfsched/halfsched_check.cpp proves the hazards
 // on them (every (h, I, K) once, K ascending, pairs agree on slot and halves,
 // no slot shared within a step, every y read after its write, no y write under
-// a later reader, 136 C tile loads: 16 C diagonal + 120 C pairs).
+// a later reader, 136 C tile loads: 16 C diagonal + 120 C pairs).  The flag
+// words of the product-first sums (below) ride on the same hazards.
 #pragma once
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
@@ -99,6 +100,31 @@ PQP_HS_HD int y_write_buf(int h) { return (h + 1) & 1; }
 
 // an active wave at its last k-block runs the update's epilogue in that step
 PQP_HS_HD bool last_kblock(int T, int wave) { return kblock_of(T, wave) == kWaves - 1; }
+
+// Flag words of the product-first sums (k_batch_half<true>): an off-diagonal
+// tile is summed in the cheaper form only while all of its q are finite and
+// every y of the k-block is finite with its sign bit clear; a set flag sends
+// the wave to the lean form for that step.
+//  - One word per slot and half, written by the wave that loads the half, with
+//    the half itself, before the step's first barrier, and read after it by
+//    the pair's two waves: the tile's own hazard (no slot shared in a step).
+//  - One word per y buffer and k-block: wave I alone writes k-block I of the
+//    iterate (from Y0 before the first barrier, from its epilogue afterwards)
+//    and the block's flag in the same place.  The flag has the writer, the
+//    step and the readers of the y block it describes, so the y checks of
+//    tests/halfsched/halfsched_check.cpp (every read a step after its write,
+//    no write under a later reader) hold for it as they stand.
+constexpr int kFlagWords = 2 * kSlots + 2 * kWaves;
+PQP_HS_HD int tile_flag(int T, int wave, int half) { return 2 * slot(T, wave) + half; }  // half: 0 or 1
+PQP_HS_HD int y_flag(int buf, int kblock) { return 2 * kSlots + buf * kWaves + kblock; }
+// the half a load_halves() mask of one half names
+PQP_HS_HD int half_of(int halves) { return halves >> 1; }
+// y (as its bits) is not finite, or has its sign bit set (-0 too)
+PQP_HS_HD bool y_dirty(unsigned bits) { return !(bits < 0x7f800000u); }
+// sticky fold over a half-tile's q, from s = +0: NaN from the first inf or NaN
+// q on (q * 0), +0 before it; q_dirty(s) tests the fold
+PQP_HS_HD float q_fold(float s, float q) { return __builtin_fmaf(q, 0.0f, s); }
+PQP_HS_HD bool q_dirty(float s) { return s != s; }
 
 }  // namespace hs
 }  // namespace pqp

@@ -505,7 +505,61 @@ __device__ __forceinline__ void half_tile_sum(float& ap, float& an, const float*
         }
     }
 }
-constexpr size_t kHalfLdsBytes = ((size_t)2 * 1024 + (size_t)hs::kSlots * hs::kTileWords) * sizeof(float);
+// The product-first form of the 64 k of an off-diagonal tile (mid2_rblock's PF
+// arithmetic): p = q y_k, two k per v_pk_mul_f32, then den += max(0, p) and
+// num += max(0, -p) in k order.  The same bits as lean1 while every q of the
+// tile is finite and every y of the k-block finite with its sign bit clear:
+// 0 * y is +0 then, a term differs from lean1's at most in a zero's sign, and
+// the sums start at +0 and never reach -0, so x + (-0) == x + (+0) for every x
+// they hold (tests/halfsched/half_pf_check.cpp walks the special values).  The
+// kernel decides both conditions itself, per wave and step.
+typedef float hf2 __attribute__((ext_vector_type(2)));
+template <int SK>
+__device__ __forceinline__ void half_tile_sum_pf(float& ap, float& an, const float* __restrict__ q,
+                                                 const float* __restrict__ yk) {
+    // 16 k per pass fit here (the form holds no 0 * y and no selects; 122 VGPRs either way): 14.94-15.06 ms
+    // per launch against 15.11-15.20 with 8, one process, profiles/r08/iterate_ab_ch16.json
+    constexpr int CH = 16;
+    hf2 acc = {ap, an};
+#pragma unroll 1
+    for (int c = 0; c < hs::kTile; c += CH) {
+        float qv[CH];
+#pragma unroll
+        for (int j = 0; j < CH; ++j) qv[j] = q[(c + j) * SK];
+#pragma unroll
+        for (int j = 0; j < CH; j += 4) {
+            const float4 yv = *reinterpret_cast<const float4*>(yk + c + j);
+            const hf2 p01 = hf2{qv[j + 0], qv[j + 1]} * hf2{yv.x, yv.y};
+            const hf2 p23 = hf2{qv[j + 2], qv[j + 3]} * hf2{yv.z, yv.w};
+#pragma unroll
+            for (int h = 0; h < 4; ++h) {
+                const float p = h < 2 ? p01[h] : p23[h - 2];
+                float tp, tn;
+                asm("v_max_f32 %0, %1, 0" : "=v"(tp) : "v"(p));
+                asm("v_max_f32_e64 %0, -%1, 0" : "=v"(tn) : "v"(p));
+                acc += hf2{tp, tn};
+            }
+        }
+    }
+    ap = acc.x;
+    an = acc.y;
+}
+// the two conditions, by the predicates of pqp_halfsched.h (which
+// half_pf_check.cpp tests on the host): is any lane's y dirty, and the sticky
+// fold over the four q of one load
+__device__ __forceinline__ int half_y_flag(float y) {
+    return __builtin_amdgcn_ballot_w64(hs::y_dirty(__float_as_uint(y))) != 0;
+}
+__device__ __forceinline__ float half_q_fold(float s, f32x4 q) {
+    return hs::q_fold(hs::q_fold(hs::q_fold(hs::q_fold(s, q.x), q.y), q.z), q.w);
+}
+// LDS: the y ping-pong, the tile slots, then the flag words (pqp_halfsched.h)
+constexpr size_t kHalfLdsBytes =
+    ((size_t)2 * 1024 + (size_t)hs::kSlots * hs::kTileWords + hs::kFlagWords) * sizeof(float);
+static_assert(kHalfLdsBytes <= 160 * 1024, "k_batch_half: LDS of a gfx950 CU");
+// PF: off-diagonal tiles take half_tile_sum_pf where the flags allow it (the
+// lean form otherwise); !PF: the lean form only (iterate_half 2, the A/B arm)
+template <bool PF>
 __global__ void __launch_bounds__(1024) k_batch_half(const float* __restrict__ QdT, long long qstride, int ldq,
                                                      const float* __restrict__ theta, const float* __restrict__ Fd,
                                                      int ldv, const float* Y0, float* Y, int updates) {
@@ -514,14 +568,20 @@ __global__ void __launch_bounds__(1024) k_batch_half(const float* __restrict__ Q
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* ybuf = lds;           // [2][N]: update h reads hs::y_read_buf(h), writes the other
     float* tiles = lds + 2 * N;  // [hs::kSlots][hs::kTileWords]
+    int* flags = reinterpret_cast<int*>(tiles + hs::kSlots * hs::kTileWords);  // [hs::kFlagWords]
     const int b = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const float* Q = QdT + (size_t)b * (size_t)qstride;
     const int row = hs::kTile * wave + lane;
     // Y0 may alias Y: this problem's Y0 is in LDS before any of its Y is written
-    ybuf[tid] = Y0 ? Y0[(size_t)b * ldv + tid] : 1000.0f;  // initMat(Y,1000) :710
+    const float ys = Y0 ? Y0[(size_t)b * ldv + tid] : 1000.0f;  // initMat(Y,1000) :710
+    ybuf[tid] = ys;
     ybuf[N + tid] = 0.0f;
+    if constexpr (PF) {  // wave I writes k-block I of the iterate and its flag, here and in its epilogue
+        flags[hs::y_flag(0, wave)] = half_y_flag(ys);
+        flags[hs::y_flag(1, wave)] = 1;
+    }
     const float th = theta[(size_t)b * ldv + row];
     const float f = Fd[(size_t)b * ldv + row];
     // this lane's part of a tile: rows lr .. lr + 3 of k lk, lk + 4, ...
@@ -546,10 +606,17 @@ __global__ void __launch_bounds__(1024) k_batch_half(const float* __restrict__ Q
         const int halves = hs::load_halves(T, wave, updates);
         if (halves == 0) return;
         float* dst = tiles + hs::slot(T, wave) * hs::kTileWords + (hs::first_half_col(halves) + lk) * hs::kTileStride + lr;
+        float fold = 0.0f;
 #pragma unroll
         for (int j = 0; j < HL; ++j) {
             float* d = dst + 4 * j * hs::kTileStride;
             d[0] = pa[j].x, d[1] = pa[j].y, d[2] = pa[j].z, d[3] = pa[j].w;
+            if constexpr (PF) fold = half_q_fold(fold, pa[j]);
+        }
+        if constexpr (PF) {  // a diagonal tile is summed in the literal form whatever it holds
+            if (halves != 3)
+                flags[hs::tile_flag(T, wave, hs::half_of(halves))] =
+                    __builtin_amdgcn_ballot_w64(hs::q_dirty(fold)) != 0;
         }
         if (halves == 3) {
 #pragma unroll
@@ -576,15 +643,28 @@ __global__ void __launch_bounds__(1024) k_batch_half(const float* __restrict__ Q
             if (K == 0) ap = an = 0.0f;
             if (hs::diagonal(T, wave))
                 half_tile_sum<hs::kTileStride, true>(ap, an, tile + lane, yk, lane, th);
-            else if (hs::transposed(T, wave))  // row * 65 + k
-                half_tile_sum<1, false>(ap, an, tile + lane * hs::kTileStride, yk, lane, th);
-            else  // k * 65 + row
-                half_tile_sum<hs::kTileStride, false>(ap, an, tile + lane, yk, lane, th);
+            else {
+                bool fast = false;
+                if constexpr (PF) {
+                    const int dirty = flags[hs::tile_flag(T, wave, 0)] | flags[hs::tile_flag(T, wave, 1)] |
+                                      flags[hs::y_flag(hs::y_read_buf(h), K)];
+                    fast = __builtin_amdgcn_readfirstlane(dirty) == 0;
+                }
+                if (hs::transposed(T, wave)) {  // row * 65 + k
+                    if (fast) half_tile_sum_pf<1>(ap, an, tile + lane * hs::kTileStride, yk);
+                    else half_tile_sum<1, false>(ap, an, tile + lane * hs::kTileStride, yk, lane, th);
+                } else {  // k * 65 + row
+                    if (fast) half_tile_sum_pf<hs::kTileStride>(ap, an, tile + lane, yk);
+                    else half_tile_sum<hs::kTileStride, false>(ap, an, tile + lane, yk, lane, th);
+                }
+            }
             if (hs::last_kblock(T, wave)) {
                 const float num = an + 1.0f * max_ref(0.0f, -f);  // matrixAdd(num, Fdn, 1) :611
                 const float den = ap + 1.0f * max_ref(0.0f, f);   // matrixAdd(den, Fdp, 1) :612
                 const float yn = num / den * cur[row];            // updY :594
                 ybuf[hs::y_write_buf(h) * N + row] = yn;
+                if constexpr (PF)
+                    flags[hs::y_flag(hs::y_write_buf(h), wave)] = half_y_flag(yn);
                 if (h == updates - 1) Y[(size_t)b * ldv + row] = yn;
             }
         }
@@ -5046,17 +5126,22 @@ static hipError_t launch_batch_iterate_one(int B, const float* QdT, long long qs
 
 // Every Qd bit-symmetric (the caller's contract): k_batch_half at n_dual 1024
 // under k_batch_resident's layout bounds, launch_batch_iterate otherwise or
-// with the iterate_half knob at 0.
+// with the iterate_half knob at 0.  Knob 1: the product-first sums where the
+// kernel finds tile and iterate finite; 2: the lean form only (same bits).
 hipError_t launch_batch_iterate_sym(int B, const float* QdT, long long qstride, int ldq, int N, const float* theta,
                                     const float* Fd, int ldv, const float* Y0, float* Y, int updates, hipStream_t s) {
-    if (!g_tune.iterate_half || N != 1024 || ldq != 1024 || qstride < (long long)N * ldq ||
-        qstride * 4 > 0x7fffffffLL)
+    const int half = g_tune.iterate_half;
+    if (!half || N != 1024 || ldq != 1024 || qstride < (long long)N * ldq || qstride * 4 > 0x7fffffffLL)
         return launch_batch_iterate(B, QdT, qstride, ldq, N, theta, Fd, ldv, Y0, Y, updates, s);
     int done = 0;
     do {
         const int c = (updates - done) < kIterPerLaunch ? (updates - done) : kIterPerLaunch;
-        hipLaunchKernelGGL(k_batch_half, dim3(B), dim3(1024), kHalfLdsBytes, s, QdT, qstride, ldq, theta, Fd, ldv,
-                           done ? Y : Y0, Y, c);
+        if (half == 2)
+            hipLaunchKernelGGL(k_batch_half<false>, dim3(B), dim3(1024), kHalfLdsBytes, s, QdT, qstride, ldq, theta, Fd,
+                               ldv, done ? Y : Y0, Y, c);
+        else
+            hipLaunchKernelGGL(k_batch_half<true>, dim3(B), dim3(1024), kHalfLdsBytes, s, QdT, qstride, ldq, theta, Fd,
+                               ldv, done ? Y : Y0, Y, c);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
         done += c;

@@ -154,7 +154,9 @@ struct Tuning {  // every tuning knob of the library (pqp_tune, include/pqp_tuni
     int iterate_kind = 0;  // pqp_batch_iterate: 0 default (k_batch_resident at N 1024, k_batch_stream at other
                            // multiples of 1024, k_batch_iterate otherwise), 1 k_batch_iterate, 2 k_batch_stream,
                            // 3 k_batch_resident without its register blocks
-    int iterate_half = 1;  // pqp_batch_iterate_sym: 1 k_batch_half where the shape fits, 0 forward to pqp_batch_iterate
+    // pqp_batch_iterate_sym where the shape fits: 1 k_batch_half with the product-first sums on finite tiles, 2 with
+    // the lean form only (the A/B arm of 1), 0 forward to pqp_batch_iterate
+    int iterate_half = 1;
     int tiny_stall = 0;  // k_solve_quintet's deciding waves return at once: every wait expires (error path)
     int persist_xcds = 0;  // k_split_persist's workgroups packed onto this many XCDs (0: 4, 8: spread over all)
     int converge_xcds = 0;  // k_converge_persist's workgroups packed onto this many XCDs (0: 6, 8: spread over all)
