@@ -585,6 +585,71 @@ int pqp_plant_create_horizon(int device, int N, int M, int nd, int ns, const flo
                              const float *Mp1, const float *Mp2, const float *Mp3, const float *Mp4,
                              const float *Mp5, const float *Mp6, pqp_plant **out);
 
+/* ----------------------------------------------------------------------
+ * 2h. The shared-plant converge solve: B states of ONE plant past the plant
+ * step's shapes (the bundled plant over 8 to 36 stages: N = 224 .. 1008).
+ * A pqp_shared keeps Qp_inv, Gp, Kp and what follows from them alone -- Qp,
+ * Qd, Theta, Gp Qp_inv -- on its device once, about 4 (2 N^2 + 5 N M + 5 M^2)
+ * bytes (the reference layouts and the kernels' padded ones); a state brings only Fp [M], Mp, Fd [N], Md (and perhaps its own Kp).
+ * No replicated ProblemBatch, no d_GQ [B][N*M].  One workgroup solves
+ * pqp_shared_states(N, M) states at a time and reads every shared matrix once
+ * for all of them (k_solve_shared).
+ *
+ * Bit-exactness: state b of pqp_shared_solve gives Y, U, h, status, Jp and Jd
+ * bit for bit equal to what pqp_batch_solve_from in PQP_MODE_CONVERGE gives
+ * problem b of a batch whose every problem holds the handle's Qd, Qp, Qp_inv,
+ * Gp and this state's Fd, Md, Fp, Mp, Kp and Y0 -- solveQuadraticDual
+ * (PQP_CPU.c:694-750) with terminate() before every update.
+ * pqp_shared_relinearize gives pqp_batch_relinearize's (that is
+ * pqp_batch_convert_to_dual's) Fd and Md.  NaN operands: as convertToDual
+ * above (positions and every non-NaN bit agree; a NaN's sign and payload may
+ * differ).
+ *
+ * Shapes: every 1 <= N <= 1024, 1 <= M <= 1024, and beyond that whatever lets
+ * two states' vectors, 2 * 4 * (4 round4(N) + 3 round4(M)) bytes, fit 160 KiB
+ * of LDS less 1 KiB; pqp_shared_states is the single answer.  Converge mode
+ * only (fixed mode: pqp_batch_iterate_shared, 2b').
+ *
+ * The handle is immutable after create and bound to its device; calls run
+ * there whatever device the caller has current, and restore the caller's.
+ * Calls on different streams may run concurrently: a solve's per-state resume
+ * words are allocated per call.  Argument errors (a null handle or pointer,
+ * B <= 0) are PQP_ERR_ARG before any device is looked for.
+ * -------------------------------------------------------------------- */
+typedef struct pqp_shared pqp_shared;
+
+/* States per workgroup the shared solve uses for (N, M); 0: unsupported shape.  No error set, no device needed. */
+int pqp_shared_states(int N, int M);
+
+/* Host pointers, reference layouts: Qp_inv [M*M], Gp [N*M], Kp [N].  device -1: the current one.
+ * Synchronous.  Derives, once, by the launchers pqp_plant_create uses (the bits of the existing entry
+ * points): Qp = Gauss_Jordan(Qp_inv), Gp Qp_inv and Qd as convertToDual forms them, Theta, and whether Qd
+ * is bit-symmetric.  An unsupported shape: PQP_ERR_ARG, *out NULL, the limit in the message. */
+int pqp_shared_create(int device, int N, int M, const float *Qp_inv, const float *Gp, const float *Kp,
+                      pqp_shared **out);
+int pqp_shared_destroy(pqp_shared *p);
+/* Host copies of what create derived; any may be NULL: Qd [N*N], Qp [M*M], theta [N], GQ [N*M] (Gp Qp_inv,
+ * row-major); *sym_out = 1 iff Qd is bit-symmetric. */
+int pqp_shared_get(pqp_shared *p, float *Qd, float *Qp, float *theta, float *GQ, int *sym_out);
+
+/* Fd [B][N], Md [B] from Fp [B][M], Mp [B]; d_Kp NULL (the handle's Kp for every state) or [B][N].
+ * ONE launch, asynchronous on `stream`, no allocation, no synchronisation. */
+int pqp_shared_relinearize(pqp_shared *p, int B, const float *d_Fp, const float *d_Mp, const float *d_Kp,
+                           float *d_Fd, float *d_Md, void *stream);
+
+/* solveQuadraticDual, converge mode, for B states.
+ * In:  d_Fd [B][N], d_Md [B], d_Fp [B][M], d_Mp [B]; d_Kp NULL or [B][N]; d_Y0 NULL (Y = 1000), a separate
+ *      [B][N] buffer, or d_Y itself (2e's warm-start rules: Y0 taken as given).  max_updates <= 0: no cap.
+ * Out: d_Y [B][N], d_U [B][M], and, each optional (NULL: not written), d_h [B] int64 (the reference's
+ *      printed h), d_status [B] (1 converged, 2 hit max_updates), d_Jp [B], d_Jd [B] (costs of the last
+ *      terminate() that passed checkFeas; NaN if none).
+ * Synchronous like pqp_batch_solve: a sequence of bounded launches on `stream` that resume from device
+ * state (the batch_chunk tuning key sets the iterates per launch, as for pqp_batch_solve). */
+int pqp_shared_solve(pqp_shared *p, int B, const float *d_Fd, const float *d_Md, const float *d_Fp,
+                     const float *d_Mp, const float *d_Kp, long long max_updates, const float *d_Y0,
+                     float *d_Y, float *d_U, long long *d_h, int *d_status, float *d_Jp, float *d_Jd,
+                     void *stream);
+
 #ifdef __cplusplus
 }
 #endif

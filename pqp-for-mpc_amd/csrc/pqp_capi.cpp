@@ -23,6 +23,7 @@
 #include "pqp_plant.h"
 #include "pqp_relin.h"
 #include "pqp_shared.h"
+#include "pqp_shared_solve.h"
 
 namespace pqp {
 
@@ -424,6 +425,18 @@ struct pqp_plant {
     pqp::DevBuf Qinv, Gp, Kp, Qp, Qd, GQ, theta;
     pqp::DevBuf Fp1, Fp2, Fp3, Mp1, Mp2, Mp3, Mp4, Mp5, Mp6;
     pqp::PlantData data{};
+};
+
+// One plant's shared data for the shared-plant converge solve (pqp_shared_*, 2h): the primal data as
+// given, what create derived, and the padded k-major layouts k_solve_shared / k_relin_shared read
+// (pqp_shared_solve.h).  Immutable after create; a call writes only the caller's buffers.
+struct pqp_shared {
+    int N = 0, M = 0, ldq = 0, ldm = 0;
+    int S = 0;     // states per workgroup (pqp_shared_states)
+    int dev = -1;  // the device it was made on (its calls run there)
+    int sym = 0;   // Qd bit-symmetric: QdR is its own column-major copy
+    pqp::DevBuf Qinv, Gp, Kp, Qp, Qd, GQ, theta;
+    pqp::DevBuf QdR, QdT, GpP, GpT, QinvT, QinvR, QpP, GQT;
 };
 
 namespace pqp {
@@ -1140,7 +1153,7 @@ using namespace pqp;
 
 extern "C" {
 
-int pqp_version(void) { return 110; }  // ABI revision: INTEGRATION.md section 6
+int pqp_version(void) { return 111; }  // ABI revision: INTEGRATION.md section 6
 
 // ---------------------------------------------------------------------------
 // 2a. status-returning host API
@@ -2161,6 +2174,152 @@ int pqp_plant_step(pqp_plant* p, int B, const float* d_x, const float* d_D, cons
         return PQP_OK;
     }
     PQP_HIP(launch_plant_step(p->data, S, p->slots[pipe ? 1 : 0], pipe, static_cast<hipStream_t>(stream)));
+    return PQP_OK;
+}
+
+// ---------------------------------------------------------------------------
+// 2h. the shared-plant converge solve: B states of one plant on one resident Qd
+// ---------------------------------------------------------------------------
+int pqp_shared_states(int N, int M) { return pqp::solve_shared_states(N, M); }
+
+int pqp_shared_create(int device, int N, int M, const float* Qp_inv, const float* Gp, const float* Kp,
+                      pqp_shared** out) {
+    if (!out) return set_error(PQP_ERR_ARG, "pqp_shared_create: null handle pointer");
+    *out = nullptr;
+    if (N <= 0 || M <= 0) return set_error(PQP_ERR_ARG, "pqp_shared_create: N = %d, M = %d must be positive", N, M);
+    const int S = pqp::solve_shared_states(N, M);
+    if (S == 0)
+        return set_error(PQP_ERR_ARG, "pqp_shared_create: (N=%d, M=%d) is not a shape pqp_shared_solve runs: two states' "
+                                      "vectors, 2 * 4 * (4 * round4(N) + 3 * round4(M)) bytes, must fit %zu bytes of LDS "
+                                      "(160 KiB less %zu)", N, M, kSolveSharedLdsBudget - kSolveSharedStaticLds,
+                         kSolveSharedStaticLds);
+    if (!Qp_inv || !Gp || !Kp) return set_error(PQP_ERR_ARG, "pqp_shared_create: null input");
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return set_error(PQP_ERR_NO_DEVICE, "libpqp: no HIP device visible");
+    if (device < 0 && hipGetDevice(&device) != hipSuccess)
+        return set_error(PQP_ERR_NO_DEVICE, "libpqp: cannot query the current device");
+    if (device >= n) return set_error(PQP_ERR_ARG, "pqp_shared_create: device %d of %d", device, n);
+    DeviceGuard on(device);
+    PQP_TRY(ensure_device());
+    hipStream_t s = lib_stream();
+    std::unique_ptr<pqp_shared> P(new pqp_shared());
+    const int ldq = round4(N), ldm = round4(M);
+    P->N = N, P->M = M, P->ldq = ldq, P->ldm = ldm, P->S = S, P->dev = device;
+    PQP_TRY(upload(P->Qinv, Qp_inv, (size_t)M * M, s));
+    PQP_TRY(upload(P->Gp, Gp, (size_t)N * M, s));
+    PQP_TRY(upload(P->Kp, Kp, N, s));
+    PQP_TRY(P->Qp.floats((size_t)M * M));
+    PQP_TRY(P->Qd.floats((size_t)N * N));
+    PQP_TRY(P->GQ.floats((size_t)N * M));
+    PQP_TRY(P->theta.floats(N));
+    // what every state shares, once, by the launchers plant_create and the batched entry points use (B = 1)
+    DevBuf aug, fac, symd;
+    PQP_TRY(aug.floats(gauss_jordan_aug_floats(M)));
+    PQP_TRY(fac.floats(M));
+    PQP_TRY(symd.alloc(sizeof(int)));
+    const long long nm = (long long)N * M, mm = (long long)M * M, nn = (long long)N * N;
+    PQP_HIP(launch_gauss_jordan_b(1, P->Qinv.f(), aug.f(), fac.f(), P->Qp.f(), M, s));                       // Qp :251
+    PQP_HIP(launch_matmul_seq_b(1, P->GQ.f(), P->Gp.f(), 0, P->Qinv.f(), 0, N, M, M, nm, mm, nm, s));      // Gp Qp_inv :492
+    PQP_HIP(launch_matmul_seq_b(1, P->Qd.f(), P->GQ.f(), 0, P->Gp.f(), 1, N, M, N, nm, nm, nn, s));        // Qd :440-455
+    PQP_HIP(launch_theta_rows(P->Qd.f(), N, N, N, P->theta.f(), s));                                       // Theta :503-519
+    PQP_HIP(launch_check_symmetric(1, P->Qd.f(), N, static_cast<int*>(symd.p), s));
+    int hsym = 0;
+    PQP_HIP(hipMemcpyAsync(&hsym, symd.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    PQP_HIP(hipStreamSynchronize(s));
+    P->sym = hsym != 0 ? 1 : 0;
+    // the kernels' layouts: rows padded to a multiple of 4 floats (zero-filled), k-major for each product
+    PQP_TRY(P->QdR.floats((size_t)N * ldq));
+    PQP_TRY(P->GpP.floats((size_t)N * ldm));
+    PQP_TRY(P->GpT.floats((size_t)M * ldq));
+    PQP_TRY(P->QinvT.floats((size_t)M * ldm));
+    PQP_TRY(P->QinvR.floats((size_t)M * ldm));
+    PQP_TRY(P->QpP.floats((size_t)M * ldm));
+    PQP_TRY(P->GQT.floats((size_t)M * ldq));
+    PQP_HIP(launch_shared_layout(P->Qd.f(), N, N, 0, P->QdR.f(), ldq, s));
+    if (!P->sym) {  // a bit-symmetric Qd is its own column-major copy
+        PQP_TRY(P->QdT.floats((size_t)N * ldq));
+        PQP_HIP(launch_shared_layout(P->Qd.f(), N, N, 1, P->QdT.f(), ldq, s));
+    }
+    PQP_HIP(launch_shared_layout(P->Gp.f(), N, M, 0, P->GpP.f(), ldm, s));
+    PQP_HIP(launch_shared_layout(P->Gp.f(), M, N, 1, P->GpT.f(), ldq, s));
+    PQP_HIP(launch_shared_layout(P->Qinv.f(), M, M, 1, P->QinvT.f(), ldm, s));
+    PQP_HIP(launch_shared_layout(P->Qinv.f(), M, M, 0, P->QinvR.f(), ldm, s));
+    PQP_HIP(launch_shared_layout(P->Qp.f(), M, M, 0, P->QpP.f(), ldm, s));
+    PQP_HIP(launch_shared_layout(P->GQ.f(), M, N, 1, P->GQT.f(), ldq, s));
+    PQP_HIP(hipStreamSynchronize(s));  // the host arrays and the Gauss_Jordan scratch are free after it
+    *out = P.release();
+    return PQP_OK;
+}
+
+int pqp_shared_destroy(pqp_shared* p) {
+    if (!p) return PQP_OK;
+    DeviceGuard on(p->dev);
+    delete p;
+    return PQP_OK;
+}
+
+int pqp_shared_get(pqp_shared* p, float* Qd, float* Qp, float* theta, float* GQ, int* sym_out) {
+    if (!p) return set_error(PQP_ERR_ARG, "pqp_shared_get: null handle");
+    DeviceGuard on(p->dev);
+    PQP_TRY(ensure_device());
+    hipStream_t s = lib_stream();
+    if (Qd) PQP_TRY(download(Qd, p->Qd.p, (size_t)p->N * p->N, s));
+    if (Qp) PQP_TRY(download(Qp, p->Qp.p, (size_t)p->M * p->M, s));
+    if (theta) PQP_TRY(download(theta, p->theta.p, p->N, s));
+    if (GQ) PQP_TRY(download(GQ, p->GQ.p, (size_t)p->N * p->M, s));
+    PQP_HIP(hipStreamSynchronize(s));
+    if (sym_out) *sym_out = p->sym;
+    return PQP_OK;
+}
+
+int pqp_shared_relinearize(pqp_shared* p, int B, const float* d_Fp, const float* d_Mp, const float* d_Kp, float* d_Fd,
+                           float* d_Md, void* stream) {
+    if (!p) return set_error(PQP_ERR_ARG, "pqp_shared_relinearize: null handle");
+    if (B <= 0) return set_error(PQP_ERR_ARG, "pqp_shared_relinearize: B = %d states", B);
+    if (!d_Fp || !d_Mp || !d_Fd || !d_Md)
+        return set_error(PQP_ERR_ARG, "pqp_shared_relinearize: null d_Fp, d_Mp, d_Fd or d_Md");
+    SharedRelinArgs a{};
+    a.GQT = p->GQT.f(), a.QinvR = p->QinvR.f(), a.Kp = p->Kp.f();
+    a.Fp = d_Fp, a.Mp = d_Mp, a.KpB = d_Kp, a.Fd = d_Fd, a.Md = d_Md;
+    a.N = p->N, a.M = p->M, a.ldq = p->ldq, a.ldm = p->ldm, a.B = B;
+    DeviceGuard on(p->dev);
+    PQP_HIP(launch_relin_shared(a, p->S, static_cast<hipStream_t>(stream)));
+    return PQP_OK;
+}
+
+int pqp_shared_solve(pqp_shared* p, int B, const float* d_Fd, const float* d_Md, const float* d_Fp, const float* d_Mp,
+                     const float* d_Kp, long long max_updates, const float* d_Y0, float* d_Y, float* d_U,
+                     long long* d_h, int* d_status, float* d_Jp, float* d_Jd, void* stream) {
+    if (!p) return set_error(PQP_ERR_ARG, "pqp_shared_solve: null handle");
+    if (B <= 0) return set_error(PQP_ERR_ARG, "pqp_shared_solve: B = %d states", B);
+    if (!d_Fd || !d_Md || !d_Fp || !d_Mp || !d_Y || !d_U)
+        return set_error(PQP_ERR_ARG, "pqp_shared_solve: null d_Fd, d_Md, d_Fp, d_Mp, d_Y or d_U");
+    DeviceGuard on(p->dev);
+    PQP_TRY(ensure_device());
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // per-call resume storage, as pqp_batch_solve: solves on different streams share nothing but the handle
+    DevBuf state, pending;
+    PQP_TRY(state.alloc(sizeof(SharedSolveState) * (size_t)B));
+    PQP_TRY(pending.alloc(sizeof(int)));
+    SharedSolveArgs a{};
+    a.QdR = p->QdR.f(), a.QdT = p->sym ? p->QdR.f() : p->QdT.f(), a.theta = p->theta.f();
+    a.GpP = p->GpP.f(), a.GpT = p->GpT.f(), a.QinvT = p->QinvT.f(), a.QpP = p->QpP.f(), a.Kp = p->Kp.f();
+    a.Fd = d_Fd, a.Md = d_Md, a.Fp = d_Fp, a.Mp = d_Mp, a.KpB = d_Kp;
+    a.Y = d_Y, a.U = d_U, a.h = d_h, a.status = d_status, a.Jp = d_Jp, a.Jd = d_Jd;
+    a.st = static_cast<SharedSolveState*>(state.p);
+    a.pending = static_cast<int*>(pending.p);
+    a.N = p->N, a.M = p->M, a.ldq = p->ldq, a.ldm = p->ldm, a.B = B, a.sym = p->sym;
+    a.max_updates = max_updates;
+    a.chunk = pqp::batch_chunk_for(p->N, p->M);
+    PQP_HIP(launch_shared_solve_init(B, p->N, a.st, d_Y0, d_Y, s));
+    for (;;) {  // bounded launches that resume from the device state
+        int left = 0;
+        PQP_HIP(hipMemsetAsync(pending.p, 0, sizeof(int), s));
+        PQP_HIP(launch_solve_shared(a, p->S, s));
+        PQP_HIP(hipMemcpyAsync(&left, pending.p, sizeof(int), hipMemcpyDeviceToHost, s));
+        PQP_HIP(hipStreamSynchronize(s));
+        if (left == 0) break;
+    }
     return PQP_OK;
 }
 

@@ -5956,3 +5956,5 @@ hipError_t launch_extract_state(int B, const SolveState* st, long long* h, int* 
 #include "pqp_plant_mid.hip"
 // The shared-Qd batched update (k_batch_shared): B states of one dual problem.
 #include "pqp_shared.hip"
+// The shared-plant converge solve (k_solve_shared, k_relin_shared): B states of one plant on one resident Qd.
+#include "pqp_shared_solve.hip"

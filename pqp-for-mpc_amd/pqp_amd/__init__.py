@@ -113,6 +113,12 @@ SIGNATURES = {
     "pqp_plant_get": (C.c_int, [_vp, _fp, _fp, _fp]),
     "pqp_plant_max_updates": (C.c_longlong, [_vp]),
     "pqp_plant_step": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_longlong] + [_vp] * 10 + [_vp]),
+    "pqp_shared_states": (C.c_int, [C.c_int, C.c_int]),
+    "pqp_shared_create": (C.c_int, [C.c_int] * 3 + [_fp] * 3 + [C.POINTER(C.c_void_p)]),
+    "pqp_shared_destroy": (C.c_int, [_vp]),
+    "pqp_shared_get": (C.c_int, [_vp, _fp, _fp, _fp, _fp, C.POINTER(C.c_int)]),
+    "pqp_shared_relinearize": (C.c_int, [_vp, C.c_int] + [_vp] * 5 + [_vp]),
+    "pqp_shared_solve": (C.c_int, [_vp, C.c_int] + [_vp] * 5 + [C.c_longlong] + [_vp] * 7 + [_vp]),
     "pqp_rowblock_create": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, C.POINTER(C.c_void_p)]),
     "pqp_rowblock_update": (C.c_int, [_vp, _vp, _vp, _vp]),
     "pqp_rowblock_check": (C.c_int, [_vp, _vp]),
@@ -1056,6 +1062,122 @@ class Plant:
     def close(self):
         if self._h is not None:
             lib().pqp_plant_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SharedProblem:
+    """One plant's shared data resident on the device, and the converge solve
+    of B of its states (pqp_shared_* of include/pqp.h, section 2h): Qp_inv
+    [M*M], Gp [N*M], Kp [N] in the reference's layouts; Qp, Qd, Theta and
+    Gp Qp_inv are derived once.  A state brings only Fp, Mp (and perhaps its own
+    Kp): no replicated :class:`ProblemBatch`.  Every state's numbers are those
+    of ``ProblemBatch.relinearize`` / ``ProblemBatch.solve`` on B copies, bit
+    for bit.  ``states`` is the number of states one workgroup solves at a
+    time.  All launches go to torch's current HIP stream of the handle's
+    device."""
+
+    def __init__(self, N: int, M: int, Qp_inv, Gp, Kp, device=None):
+        import torch
+
+        self.torch = torch
+        self.N, self.M = int(N), int(M)
+        self._h = None
+        self.B = 0
+        self.states = int(lib().pqp_shared_states(self.N, self.M))  # per workgroup; 0: unsupported shape
+        host = dict(Qp_inv=_f32(Qp_inv).reshape(-1), Gp=_f32(Gp).reshape(-1), Kp=_f32(Kp).reshape(-1))
+        sizes = dict(Qp_inv=self.M * self.M, Gp=self.N * self.M, Kp=self.N)
+        for k, n in sizes.items():
+            if self.states and host[k].size != n:
+                raise ValueError(f"SharedProblem: {k} has {host[k].size} values, not {n}")
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        h = C.c_void_p()
+        dev = self.device.index if self.device.index is not None else -1
+        _check(lib().pqp_shared_create(dev, self.N, self.M, _buf(host["Qp_inv"]), _buf(host["Gp"]), _buf(host["Kp"]),
+                                       C.byref(h)))
+        self._h = h
+
+    def _stream(self):
+        return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _dev(self, a, cols: int | None, what: str, B: int | None = None):
+        torch = self.torch
+        if not torch.is_tensor(a):
+            a = np.ascontiguousarray(np.asarray(a, np.float32))
+        t = torch.as_tensor(a, dtype=torch.float32, device=self.device)
+        t = (t.reshape(-1) if cols is None else t.reshape(-1, cols)).contiguous()
+        if B is not None and t.shape[0] != B:
+            raise ValueError(f"SharedProblem: {what} must hold {B} states")
+        return t
+
+    def get(self) -> dict:
+        """Host copies of what create derived: Qd [N*N], Qp [M*M], theta [N],
+        GQ [N*M] (Gp Qp_inv, row-major) and sym (1 iff Qd is bit-symmetric)."""
+        out = dict(Qd=np.zeros(self.N * self.N, np.float32), Qp=np.zeros(self.M * self.M, np.float32),
+                   theta=np.zeros(self.N, np.float32), GQ=np.zeros(self.N * self.M, np.float32))
+        sym = C.c_int(0)
+        _check(lib().pqp_shared_get(self._h, _buf(out["Qd"]), _buf(out["Qp"]), _buf(out["theta"]), _buf(out["GQ"]),
+                                    C.byref(sym)))
+        out["sym"] = int(sym.value)
+        return out
+
+    def relinearize(self, Fp, Mp, Kp=None):
+        """Fd [B, N] and Md [B] (device tensors) of the states with linear
+        terms Fp [B, M], Mp [B] and bounds Kp [B, N] (None: the handle's Kp):
+        one asynchronous launch."""
+        torch = self.torch
+        p = ProblemBatch._p
+        Fp = self._dev(Fp, self.M, "Fp")
+        B = int(Fp.shape[0])
+        Mp = self._dev(Mp, None, "Mp", B)
+        Kt = None if Kp is None else self._dev(Kp, self.N, "Kp", B)
+        Fd = torch.zeros(B, self.N, dtype=torch.float32, device=self.device)
+        Md = torch.zeros(B, dtype=torch.float32, device=self.device)
+        _check(lib().pqp_shared_relinearize(self._h, B, p(Fp), p(Mp), None if Kt is None else p(Kt), p(Fd), p(Md),
+                                            self._stream()))
+        self._relin_inputs = (Fp, Mp, Kt)  # alive until the next call: the launch is asynchronous
+        return Fd, Md
+
+    def solve(self, Fd, Md, Fp, Mp, Kp=None, Y0=None, max_updates: int = 0):
+        """The converge solve of B states: fills the device tensors Y [B, N],
+        U [B, M], h (int64), status (1 converged, 2 hit max_updates), Jp, Jd and
+        returns self.  Y0 [B, N]: the start (None: Y = 1000; ``self.Y`` itself:
+        in place).  max_updates <= 0: no cap.  Synchronous."""
+        torch = self.torch
+        p = ProblemBatch._p
+        f = dict(dtype=torch.float32, device=self.device)
+        Fd = self._dev(Fd, self.N, "Fd")
+        B = int(Fd.shape[0])
+        Md, Mp = self._dev(Md, None, "Md", B), self._dev(Mp, None, "Mp", B)
+        Fp = self._dev(Fp, self.M, "Fp", B)
+        Kt = None if Kp is None else self._dev(Kp, self.N, "Kp", B)
+        in_place = Y0 is not None and B == self.B and Y0 is self.Y
+        Y0t = None if Y0 is None else (self.Y if in_place else self._dev(Y0, self.N, "Y0", B))
+        if B != self.B:
+            self.B = B
+            self.Y, self.U = torch.zeros(B, self.N, **f), torch.zeros(B, self.M, **f)
+            self.h = torch.zeros(B, dtype=torch.int64, device=self.device)
+            self.status = torch.zeros(B, dtype=torch.int32, device=self.device)
+            self.Jp, self.Jd = torch.zeros(B, **f), torch.zeros(B, **f)
+        _check(lib().pqp_shared_solve(self._h, B, p(Fd), p(Md), p(Fp), p(Mp), None if Kt is None else p(Kt),
+                                      int(max_updates), None if Y0t is None else p(Y0t), p(self.Y), p(self.U),
+                                      p(self.h), p(self.status), p(self.Jp), p(self.Jd), self._stream()))
+        return self
+
+    def close(self):
+        if self._h is not None:
+            lib().pqp_shared_destroy(self._h)
             self._h = None
 
     def __enter__(self):
