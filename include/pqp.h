@@ -650,6 +650,66 @@ int pqp_shared_solve(pqp_shared *p, int B, const float *d_Fd, const float *d_Md,
                      float *d_Y, float *d_U, long long *d_h, int *d_status, float *d_Jp, float *d_Jd,
                      void *stream);
 
+/* ----------------------------------------------------------------------
+ * 2i. The shared plant's control step: x, D to U for B states in ONE launch.
+ * 2f / 2g give the two small size classes a control step; this is the one of
+ * the third (2h's shapes: the bundled plant over 8 to 36 stages, N up to
+ * 1024).  pqp_shared_create_plant makes a pqp_shared that also holds the
+ * plant's nine linear-term matrices; pqp_shared_step then takes B states
+ * through computeFp, computeMp, convertToDual's Fd and Md and the converge
+ * solve in one asynchronous launch (k_step_shared), where 2h's
+ * pieces take four calls, about 16 launches, 5 allocations and 3 host
+ * synchronisations.
+ *
+ * pqp_shared_step's contract is pqp_plant_step's, word for word: one launch on
+ * `stream`, asynchronous, no allocation, no synchronisation, no copy to the
+ * host, the caller's device restored, so steps can be chained on a stream or
+ * captured in a graph.  Converge mode only.  One difference: d_Fp and d_Fd are
+ * required -- one workgroup's LDS is full of iterates, so they are the step's
+ * working storage as well as its outputs.
+ *
+ * Bit-exactness: state b of a step gives exactly what pqp_batch_compute_fp and
+ * pqp_batch_compute_mp at that state, pqp_shared_relinearize and
+ * pqp_shared_solve with the same cap and start give -- Fp, Mp, Fd, Md, Y, U,
+ * h, status, Jp, Jd, bit for bit; that is computeFp (PQP_CPU.c:373), computeMp
+ * (:395), convertToDual's Fd and Md (:456-479) and solveQuadraticDual
+ * (:694-750, line :710 replaced when warm).  NaN operands: as convertToDual
+ * above (positions and every non-NaN bit agree; payloads may differ).
+ *
+ * pqp_shared_get, pqp_shared_relinearize, pqp_shared_solve and
+ * pqp_shared_destroy work on either kind of handle, with the same results.
+ * Argument errors (a null handle or required pointer, B <= 0, a cap out of
+ * range, a handle without plant matrices) are PQP_ERR_ARG before any device is
+ * looked for.
+ * -------------------------------------------------------------------- */
+
+/* States per workgroup the step uses for (N, M, nd, ns): pqp_shared_states(N, M) where the
+ * step's own words for that many states (x, D, x'Mp1, D'Mp2, D'Mp3, Fp, Fp'Qp_inv:
+ * 4 * (3 round4(ns) + 2 round4(nd) + 2 round4(M)) bytes each) fit the launch's LDS too, which
+ * they do for every nd, ns <= 64; else 0.  nd, ns >= 1.  No error set, no device needed. */
+int pqp_shared_step_states(int N, int M, int nd, int ns);
+
+/* pqp_plant_create's arguments; the result is a pqp_shared that holds everything
+ * pqp_shared_create derives (by the same launchers: the same bits) and the nine linear-term
+ * matrices in the kernel's padded layouts.  An unsupported shape (pqp_shared_step_states 0):
+ * PQP_ERR_ARG, *out NULL, the limit in the message. */
+int pqp_shared_create_plant(int device, int N, int M, int nd, int ns, const float *Qp_inv, const float *Gp,
+                            const float *Kp, const float *Fp1, const float *Fp2, const float *Fp3,
+                            const float *Mp1, const float *Mp2, const float *Mp3, const float *Mp4,
+                            const float *Mp5, const float *Mp6, pqp_shared **out);
+
+/* Largest max_updates a step accepts (batch_chunk_for(N, M)), as pqp_plant_max_updates. */
+long /* (the return type is long long; see pqp_plant_max_updates) */
+long pqp_shared_max_updates(const pqp_shared *p);
+
+/* One control step of B states: pqp_plant_step's arguments and meaning (2f), except that d_Fp [B][M]
+ * and d_Fd [B][N] are required.  d_h, d_status, d_Mp, d_Md, d_Jp, d_Jd stay optional (NULL: not
+ * written).  1 <= max_updates <= pqp_shared_max_updates(p), else PQP_ERR_ARG: every state finishes
+ * in this launch.  A handle made by pqp_shared_create (no plant matrices): PQP_ERR_ARG. */
+int pqp_shared_step(pqp_shared *p, int B, const float *d_x, const float *d_D, const float *d_Kp, int warm,
+                    long long max_updates, float *d_Y, float *d_U, long long *d_h, int *d_status,
+                    float *d_Fp, float *d_Mp, float *d_Fd, float *d_Md, float *d_Jp, float *d_Jd, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

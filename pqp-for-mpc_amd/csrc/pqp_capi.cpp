@@ -437,6 +437,9 @@ struct pqp_shared {
     int sym = 0;   // Qd bit-symmetric: QdR is its own column-major copy
     pqp::DevBuf Qinv, Gp, Kp, Qp, Qd, GQ, theta;
     pqp::DevBuf QdR, QdT, GpP, GpT, QinvT, QinvR, QpP, GQT;
+    // pqp_shared_create_plant only (2i): the linear-term matrices k_step_shared reads; nd = ns = 0 without them
+    int nd = 0, ns = 0;
+    pqp::DevBuf Fp1T, Fp2T, Fp3, Mp1P, Mp2P, Mp3P, Mp4, Mp5, Mp6;
 };
 
 namespace pqp {
@@ -1153,7 +1156,7 @@ using namespace pqp;
 
 extern "C" {
 
-int pqp_version(void) { return 111; }  // ABI revision: INTEGRATION.md section 6
+int pqp_version(void) { return 112; }  // ABI revision: INTEGRATION.md section 6
 
 // ---------------------------------------------------------------------------
 // 2a. status-returning host API
@@ -2182,23 +2185,40 @@ int pqp_plant_step(pqp_plant* p, int B, const float* d_x, const float* d_D, cons
 // ---------------------------------------------------------------------------
 int pqp_shared_states(int N, int M) { return pqp::solve_shared_states(N, M); }
 
-int pqp_shared_create(int device, int N, int M, const float* Qp_inv, const float* Gp, const float* Kp,
-                      pqp_shared** out) {
-    if (!out) return set_error(PQP_ERR_ARG, "pqp_shared_create: null handle pointer");
+// The nine linear-term matrices of a plant (pqp_shared_create_plant), host pointers in the reference layouts.
+struct SharedPlantIn {
+    int nd, ns;
+    const float *Fp1, *Fp2, *Fp3, *Mp1, *Mp2, *Mp3, *Mp4, *Mp5, *Mp6;
+};
+
+// pqp_shared_create (lin NULL) and pqp_shared_create_plant: `fn` names the caller in messages
+static int shared_create(const char* fn, int device, int N, int M, const float* Qp_inv, const float* Gp,
+                         const float* Kp, const SharedPlantIn* lin, pqp_shared** out) {
+    if (!out) return set_error(PQP_ERR_ARG, "%s: null handle pointer", fn);
     *out = nullptr;
-    if (N <= 0 || M <= 0) return set_error(PQP_ERR_ARG, "pqp_shared_create: N = %d, M = %d must be positive", N, M);
+    if (N <= 0 || M <= 0) return set_error(PQP_ERR_ARG, "%s: N = %d, M = %d must be positive", fn, N, M);
+    if (lin && (lin->nd <= 0 || lin->ns <= 0))
+        return set_error(PQP_ERR_ARG, "%s: nd = %d, ns = %d must be positive", fn, lin->nd, lin->ns);
     const int S = pqp::solve_shared_states(N, M);
     if (S == 0)
-        return set_error(PQP_ERR_ARG, "pqp_shared_create: (N=%d, M=%d) is not a shape pqp_shared_solve runs: two states' "
+        return set_error(PQP_ERR_ARG, "%s: (N=%d, M=%d) is not a shape pqp_shared_solve runs: two states' "
                                       "vectors, 2 * 4 * (4 * round4(N) + 3 * round4(M)) bytes, must fit %zu bytes of LDS "
-                                      "(160 KiB less %zu)", N, M, kSolveSharedLdsBudget - kSolveSharedStaticLds,
+                                      "(160 KiB less %zu)", fn, N, M, kSolveSharedLdsBudget - kSolveSharedStaticLds,
                          kSolveSharedStaticLds);
-    if (!Qp_inv || !Gp || !Kp) return set_error(PQP_ERR_ARG, "pqp_shared_create: null input");
+    if (lin && pqp::step_shared_states(N, M, lin->nd, lin->ns) == 0)
+        return set_error(PQP_ERR_ARG, "%s: (N=%d, M=%d, nd=%d, ns=%d) is not a shape pqp_shared_step runs: the step's "
+                                      "words of %d states, %d * 4 * (3 * round4(ns) + 2 * round4(nd) + 2 * round4(M)) "
+                                      "bytes, must fit %zu bytes of LDS (160 KiB less %zu)", fn, N, M, lin->nd, lin->ns,
+                         S, S, kSolveSharedLdsBudget - kSolveSharedStaticLds, kSolveSharedStaticLds);
+    if (!Qp_inv || !Gp || !Kp) return set_error(PQP_ERR_ARG, "%s: null input", fn);
+    if (lin && (!lin->Fp1 || !lin->Fp2 || !lin->Fp3 || !lin->Mp1 || !lin->Mp2 || !lin->Mp3 || !lin->Mp4 || !lin->Mp5 ||
+                !lin->Mp6))
+        return set_error(PQP_ERR_ARG, "%s: null input", fn);
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return set_error(PQP_ERR_NO_DEVICE, "libpqp: no HIP device visible");
     if (device < 0 && hipGetDevice(&device) != hipSuccess)
         return set_error(PQP_ERR_NO_DEVICE, "libpqp: cannot query the current device");
-    if (device >= n) return set_error(PQP_ERR_ARG, "pqp_shared_create: device %d of %d", device, n);
+    if (device >= n) return set_error(PQP_ERR_ARG, "%s: device %d of %d", fn, device, n);
     DeviceGuard on(device);
     PQP_TRY(ensure_device());
     hipStream_t s = lib_stream();
@@ -2246,9 +2266,39 @@ int pqp_shared_create(int device, int N, int M, const float* Qp_inv, const float
     PQP_HIP(launch_shared_layout(P->Qinv.f(), M, M, 0, P->QinvR.f(), ldm, s));
     PQP_HIP(launch_shared_layout(P->Qp.f(), M, M, 0, P->QpP.f(), ldm, s));
     PQP_HIP(launch_shared_layout(P->GQ.f(), M, N, 1, P->GQT.f(), ldq, s));
+    DevBuf in[5];  // the uploaded Fp1, Fp2, Mp1, Mp2, Mp3, alive until their padded copies are made
+    if (lin) {
+        // the step's matrices: k-major for its products, rows padded like the rest
+        const int nd = lin->nd, ns = lin->ns, ldd = round4(nd), ldx = round4(ns);
+        P->nd = nd, P->ns = ns;
+        PQP_TRY(upload(in[0], lin->Fp1, (size_t)M * nd, s));
+        PQP_TRY(upload(in[1], lin->Fp2, (size_t)M * ns, s));
+        PQP_TRY(upload(in[2], lin->Mp1, (size_t)ns * ns, s));
+        PQP_TRY(upload(in[3], lin->Mp2, (size_t)nd * ns, s));
+        PQP_TRY(upload(in[4], lin->Mp3, (size_t)nd * nd, s));
+        PQP_TRY(upload(P->Fp3, lin->Fp3, M, s));
+        PQP_TRY(upload(P->Mp4, lin->Mp4, ns, s));
+        PQP_TRY(upload(P->Mp5, lin->Mp5, nd, s));
+        PQP_TRY(upload(P->Mp6, lin->Mp6, 1, s));
+        PQP_TRY(P->Fp1T.floats((size_t)nd * ldm));
+        PQP_TRY(P->Fp2T.floats((size_t)ns * ldm));
+        PQP_TRY(P->Mp1P.floats((size_t)ns * ldx));
+        PQP_TRY(P->Mp2P.floats((size_t)nd * ldx));
+        PQP_TRY(P->Mp3P.floats((size_t)nd * ldd));
+        PQP_HIP(launch_shared_layout(in[0].f(), nd, M, 1, P->Fp1T.f(), ldm, s));
+        PQP_HIP(launch_shared_layout(in[1].f(), ns, M, 1, P->Fp2T.f(), ldm, s));
+        PQP_HIP(launch_shared_layout(in[2].f(), ns, ns, 0, P->Mp1P.f(), ldx, s));
+        PQP_HIP(launch_shared_layout(in[3].f(), nd, ns, 0, P->Mp2P.f(), ldx, s));
+        PQP_HIP(launch_shared_layout(in[4].f(), nd, nd, 0, P->Mp3P.f(), ldd, s));
+    }
     PQP_HIP(hipStreamSynchronize(s));  // the host arrays and the Gauss_Jordan scratch are free after it
     *out = P.release();
     return PQP_OK;
+}
+
+int pqp_shared_create(int device, int N, int M, const float* Qp_inv, const float* Gp, const float* Kp,
+                      pqp_shared** out) {
+    return shared_create("pqp_shared_create", device, N, M, Qp_inv, Gp, Kp, nullptr, out);
 }
 
 int pqp_shared_destroy(pqp_shared* p) {
@@ -2320,6 +2370,58 @@ int pqp_shared_solve(pqp_shared* p, int B, const float* d_Fd, const float* d_Md,
         PQP_HIP(hipStreamSynchronize(s));
         if (left == 0) break;
     }
+    return PQP_OK;
+}
+
+// ---------------------------------------------------------------------------
+// 2i. the shared plant's control step: x, D to U for B states in one launch
+// ---------------------------------------------------------------------------
+int pqp_shared_step_states(int N, int M, int nd, int ns) { return pqp::step_shared_states(N, M, nd, ns); }
+
+int pqp_shared_create_plant(int device, int N, int M, int nd, int ns, const float* Qp_inv, const float* Gp,
+                            const float* Kp, const float* Fp1, const float* Fp2, const float* Fp3, const float* Mp1,
+                            const float* Mp2, const float* Mp3, const float* Mp4, const float* Mp5, const float* Mp6,
+                            pqp_shared** out) {
+    const SharedPlantIn lin = {nd, ns, Fp1, Fp2, Fp3, Mp1, Mp2, Mp3, Mp4, Mp5, Mp6};
+    return shared_create("pqp_shared_create_plant", device, N, M, Qp_inv, Gp, Kp, &lin, out);
+}
+
+long long pqp_shared_max_updates(const pqp_shared* p) {
+    if (!p) return set_error(PQP_ERR_ARG, "pqp_shared_max_updates: null handle");
+    return pqp::batch_chunk_for(p->N, p->M);
+}
+
+int pqp_shared_step(pqp_shared* p, int B, const float* d_x, const float* d_D, const float* d_Kp, int warm,
+                    long long max_updates, float* d_Y, float* d_U, long long* d_h, int* d_status, float* d_Fp,
+                    float* d_Mp, float* d_Fd, float* d_Md, float* d_Jp, float* d_Jd, void* stream) {
+    if (!p) return set_error(PQP_ERR_ARG, "pqp_shared_step: null handle");
+    if (B <= 0) return set_error(PQP_ERR_ARG, "pqp_shared_step: B = %d states", B);
+    if (!d_x || !d_D || !d_Y || !d_U || !d_Fp || !d_Fd)
+        return set_error(PQP_ERR_ARG, "pqp_shared_step: null d_x, d_D, d_Y, d_U, d_Fp or d_Fd");
+    if (p->nd == 0)
+        return set_error(PQP_ERR_ARG, "pqp_shared_step: the handle was made by pqp_shared_create and has no plant "
+                                      "matrices (use pqp_shared_create_plant)");
+    const long long cap = pqp::batch_chunk_for(p->N, p->M);
+    if (max_updates < 1 || max_updates > cap)
+        return set_error(PQP_ERR_ARG, "pqp_shared_step: max_updates = %lld is outside 1 .. %lld "
+                                      "(pqp_shared_max_updates: one launch's budget)", max_updates, cap);
+    SharedStepArgs t{};
+    SharedSolveArgs& a = t.solve;
+    a.QdR = p->QdR.f(), a.QdT = p->sym ? p->QdR.f() : p->QdT.f(), a.theta = p->theta.f();
+    a.GpP = p->GpP.f(), a.GpT = p->GpT.f(), a.QinvT = p->QinvT.f(), a.QpP = p->QpP.f(), a.Kp = p->Kp.f();
+    a.Fd = d_Fd, a.Fp = d_Fp, a.KpB = d_Kp;  // Md, Mp: the kernel's own words
+    a.Y = d_Y, a.U = d_U, a.h = d_h, a.status = d_status, a.Jp = d_Jp, a.Jd = d_Jd;
+    a.N = p->N, a.M = p->M, a.ldq = p->ldq, a.ldm = p->ldm, a.B = B, a.sym = p->sym;
+    a.max_updates = max_updates;
+    a.chunk = max_updates;  // every state finishes within it
+    t.Fp1T = p->Fp1T.f(), t.Fp2T = p->Fp2T.f(), t.Fp3 = p->Fp3.f();
+    t.Mp1P = p->Mp1P.f(), t.Mp2P = p->Mp2P.f(), t.Mp3P = p->Mp3P.f();
+    t.Mp4 = p->Mp4.f(), t.Mp5 = p->Mp5.f(), t.Mp6 = p->Mp6.f();
+    t.GQT = p->GQT.f(), t.QinvR = p->QinvR.f();
+    t.x = d_x, t.D = d_D, t.Fp = d_Fp, t.Fd = d_Fd, t.Mp = d_Mp, t.Md = d_Md;
+    t.nd = p->nd, t.ns = p->ns, t.warm = warm ? 1 : 0;
+    DeviceGuard on(p->dev);
+    PQP_HIP(launch_step_shared(t, p->S, static_cast<hipStream_t>(stream)));
     return PQP_OK;
 }
 

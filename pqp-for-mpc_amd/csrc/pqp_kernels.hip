@@ -5958,3 +5958,5 @@ hipError_t launch_extract_state(int B, const SolveState* st, long long* h, int* 
 #include "pqp_shared.hip"
 // The shared-plant converge solve (k_solve_shared, k_relin_shared): B states of one plant on one resident Qd.
 #include "pqp_shared_solve.hip"
+// ... and its control step (k_step_shared): x, D to U in one launch, on the same loop.
+#include "pqp_shared_step.hip"

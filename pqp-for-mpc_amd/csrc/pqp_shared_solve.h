@@ -1,5 +1,6 @@
 // pqp_shared_solve.h -- internal interface of the shared-plant converge solve
-// (pqp_shared_solve.hip: k_solve_shared, k_relin_shared) to the host shim.
+// (pqp_shared_solve.hip: k_solve_shared, k_relin_shared) and of the shared
+// plant's control step (pqp_shared_step.hip: k_step_shared) to the host shim.
 // Not part of the C ABI.  (Beside pqp_launch.h, not in it: that header's text
 // is part of the key of the kernels' recorded counter measurements, which
 // these declarations do not touch.)
@@ -64,6 +65,42 @@ struct SharedRelinArgs {
     int N, M, ldq, ldm, B;
 };
 hipError_t launch_relin_shared(const SharedRelinArgs& a, int S, hipStream_t s);
+
+// ---- the control step (pqp_shared_step.hip: k_step_shared; pqp.h 2i) ----
+// LDS floats one state's prologue words take: x, x'Mp1, D'Mp2 ([round4(ns)] each), D, D'Mp3
+// ([round4(nd)] each), Fp and Fp'Qp_inv ([ldm] each).  They lie over the solve's vectors, which
+// are dead then, so a state takes the larger of the two.  step_shared_states, the launcher's LDS
+// size and the kernel's carve-up all go through these.
+__host__ __device__ inline size_t step_shared_prologue_floats(int M, int nd, int ns) {
+    return (size_t)3 * shared_round4(ns) + (size_t)2 * shared_round4(nd) + (size_t)2 * shared_round4(M);
+}
+__host__ __device__ inline size_t step_shared_state_floats(int N, int M, int nd, int ns) {
+    const size_t a = solve_shared_state_floats(N, M), b = step_shared_prologue_floats(M, nd, ns);
+    return a > b ? a : b;
+}
+inline size_t step_shared_lds_bytes(int N, int M, int nd, int ns, int S) {
+    return (size_t)S * step_shared_state_floats(N, M, nd, ns) * sizeof(float);
+}
+// States per workgroup k_step_shared uses: solve_shared_states(N, M) where the prologue's words
+// for that many states fit the launch's LDS too, else 0.
+int step_shared_states(int N, int M, int nd, int ns);
+
+// All device pointers.  `solve` as for k_solve_shared, with Fp / Fd the same buffers as below, Md, Mp,
+// st and pending unused, chunk = max_updates.  The plant's linear-term matrices, padded and k-major:
+//   Fp1T [nd][ldm] Fp1'     Fp2T [ns][ldm] Fp2'     Mp1P [ns][ldx] row-major Mp1
+//   Mp2P [nd][ldx] row-major Mp2                     Mp3P [nd][ldd] row-major Mp3
+//   GQT, QinvR as SharedRelinArgs;  Fp3 [M], Mp4 [ns], Mp5 [nd], Mp6 [1] as given
+// (ldx = round4(ns), ldd = round4(nd)).
+struct SharedStepArgs {
+    SharedSolveArgs solve;
+    const float *Fp1T, *Fp2T, *Fp3, *Mp1P, *Mp2P, *Mp3P, *Mp4, *Mp5, *Mp6, *GQT, *QinvR;
+    const float *x, *D;  // [B][ns], [B][nd]
+    float *Fp, *Fd;      // [B][M], [B][N]: outputs, and what the solve loop reads
+    float *Mp, *Md;      // [B] each, optional
+    int nd, ns, warm;
+};
+// one launch: every state runs to its end (max_updates <= one launch's budget)
+hipError_t launch_step_shared(const SharedStepArgs& a, int S, hipStream_t s);
 
 // dst [orows][ld] <- src (row-major orows x ocols, or, transposed, ocols x orows), columns ocols..ld-1 zeroed
 hipError_t launch_shared_layout(const float* src, int orows, int ocols, int transposed, float* dst, int ld,

@@ -275,29 +275,35 @@ __device__ __forceinline__ float cost_chain(const float* __restrict__ q, const f
     return J;
 }
 
-}  // namespace
+// The per-state control words of a workgroup (static LDS of the kernel that runs the loop):
+// h, the status (SolveStatus), this iterate's checkFeas failure, "finished at this iterate",
+// the costs of the last terminate() that passed checkFeas, and this iterate's two costs.
+struct SharedSolveCtl {
+    long long* h;
+    int *fin, *bad, *fresh;
+    float *Jp, *Jd, *jp, *jd;
+};
 
-// grid = ceil(B / S) workgroups of blockDim.x (a multiple of 64) threads;
-// dynamic LDS = S * solve_shared_state_floats(N, M) floats.
-template <int S>
-__global__ void __launch_bounds__(kSolveSharedThreads) k_solve_shared(SharedSolveArgs A) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    __shared__ long long s_h[S];
-    __shared__ int s_fin[S], s_bad[S], s_new[S];
-    __shared__ float s_Jp[S], s_Jd[S], s_jp[S], s_jd[S];
+// The loop of PQP_CPU.c:718-746 -- terminate(), then updateY2 -- for the S states of one workgroup
+// (k_solve_shared and k_step_shared: the same text, so the same arithmetic).  In: the control words
+// of c, the iterates as the first image of lds ([ldq][S]; the second zero) and a barrier after both;
+// md / mp: Md and Mp of state s at [s].  A state that finishes has its Y, U, h, status and costs
+// written at that moment (RESUME: its resume words too).  Leaves when no state is running or
+// A.chunk updates were made; returns the states still running, `cur` the image of their iterate.
+template <int S, bool RESUME>
+__device__ __forceinline__ int shared_converge_loop(const SharedSolveArgs& A, int b0, int ns, float* lds,
+                                                    const SharedSolveCtl& c, const float* md, const float* mp,
+                                                    float*& cur) {
     const int tid = threadIdx.x, NT = blockDim.x;
     const int N = A.N, M = A.M, ldq = A.ldq, ldm = A.ldm;
-    const int b0 = blockIdx.x * S;
-    const int ns = (A.B - b0) < S ? (A.B - b0) : S;  // states of this block
-    if (tid < S) {
-        SharedSolveState z;
-        z.h = 0, z.status = kStatusDone, z.Jp = z.Jd = 0.0f;  // a missing state: finished, never written
-        if (tid < ns) z = A.st[b0 + tid];
-        s_h[tid] = z.h, s_fin[tid] = z.status, s_Jp[tid] = z.Jp, s_Jd[tid] = z.Jd;
-        s_bad[tid] = s_new[tid] = 0;
-    }
-    int left = __syncthreads_count(tid < S && s_fin[tid] == kStatusContinue);
-    if (left == 0) return;  // every state finished in an earlier launch
+    long long* const s_h = c.h;
+    int* const s_fin = c.fin;
+    int* const s_bad = c.bad;
+    int* const s_new = c.fresh;
+    float* const s_Jp = c.Jp;
+    float* const s_Jd = c.Jd;
+    float* const s_jp = c.jp;
+    float* const s_jd = c.jd;
     float* ya = lds;                       // [ldq][S]
     float* yb = ya + (size_t)S * ldq;      // [ldq][S]
     float* tq = yb + (size_t)S * ldq;      // [ldq][S]  Y'Qd row, then its terms (Jd)
@@ -305,15 +311,8 @@ __global__ void __launch_bounds__(kSolveSharedThreads) k_solve_shared(SharedSolv
     float* tM = fy + (size_t)S * ldq;      // [ldm][S]  Gp'Y + Fp, then the Fp.U terms
     float* Us = tM + (size_t)S * ldm;      // [ldm][S]  U
     float* tu = Us + (size_t)S * ldm;      // [ldm][S]  U'Qp row, then its terms (Jp)
-    for (int s = 0; s < S; ++s) {
-        const float* y0 = (s < ns && s_fin[s] == kStatusContinue) ? A.Y + (size_t)(b0 + s) * N : nullptr;
-        for (int i = tid; i < ldq; i += NT) {
-            ya[(size_t)i * S + s] = (y0 && i < N) ? y0[i] : 0.0f;
-            yb[(size_t)i * S + s] = 0.0f;
-        }
-    }
-    __syncthreads();
-    float* cur = ya;
+    int left = 0;
+    cur = ya;
     float* nxt = yb;
     bool was_feasible = false;
     long long done_here = 0;
@@ -368,8 +367,8 @@ __global__ void __launch_bounds__(kSolveSharedThreads) k_solve_shared(SharedSolv
                 }
             }
             __syncthreads();
-            if (tid < ns) s_jd[tid] = cost_chain(tq, fy, N, S, tid, A.Md[b0 + tid]);
-            else if (tid >= cb && tid < cb + ns) s_jp[tid - cb] = cost_chain(tu, tM, M, S, tid - cb, A.Mp[b0 + tid - cb]);
+            if (tid < ns) s_jd[tid] = cost_chain(tq, fy, N, S, tid, md[tid]);
+            else if (tid >= cb && tid < cb + ns) s_jp[tid - cb] = cost_chain(tu, tM, M, S, tid - cb, mp[tid - cb]);
             __syncthreads();
         }
         was_feasible = any_feasible;
@@ -392,7 +391,7 @@ __global__ void __launch_bounds__(kSolveSharedThreads) k_solve_shared(SharedSolv
                     fresh = 1;
                     SharedSolveState z;
                     z.h = h, z.status = fin, z.pad = 0, z.Jp = s_Jp[s], z.Jd = s_Jd[s];
-                    A.st[b0 + s] = z;
+                    if constexpr (RESUME) A.st[b0 + s] = z;
                     if (A.h) A.h[b0 + s] = h;
                     if (A.status) A.status[b0 + s] = fin;
                     if (A.Jp) A.Jp[b0 + s] = z.Jp;
@@ -418,6 +417,45 @@ __global__ void __launch_bounds__(kSolveSharedThreads) k_solve_shared(SharedSolv
         if (tid < S && s_fin[tid] == kStatusContinue) ++s_h[tid];
         ++done_here;
     }
+    return left;
+}
+
+}  // namespace
+
+// grid = ceil(B / S) workgroups of blockDim.x (a multiple of 64) threads;
+// dynamic LDS = S * solve_shared_state_floats(N, M) floats.
+template <int S>
+__global__ void __launch_bounds__(kSolveSharedThreads) k_solve_shared(SharedSolveArgs A) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    __shared__ long long s_h[S];
+    __shared__ int s_fin[S], s_bad[S], s_new[S];
+    __shared__ float s_Jp[S], s_Jd[S], s_jp[S], s_jd[S];
+    const int tid = threadIdx.x, NT = blockDim.x;
+    const int N = A.N, ldq = A.ldq;
+    const int b0 = blockIdx.x * S;
+    const int ns = (A.B - b0) < S ? (A.B - b0) : S;  // states of this block
+    if (tid < S) {
+        SharedSolveState z;
+        z.h = 0, z.status = kStatusDone, z.Jp = z.Jd = 0.0f;  // a missing state: finished, never written
+        if (tid < ns) z = A.st[b0 + tid];
+        s_h[tid] = z.h, s_fin[tid] = z.status, s_Jp[tid] = z.Jp, s_Jd[tid] = z.Jd;
+        s_bad[tid] = s_new[tid] = 0;
+    }
+    int left = __syncthreads_count(tid < S && s_fin[tid] == kStatusContinue);
+    if (left == 0) return;  // every state finished in an earlier launch
+    float* ya = lds;                   // [ldq][S]
+    float* yb = ya + (size_t)S * ldq;  // [ldq][S]
+    for (int s = 0; s < S; ++s) {
+        const float* y0 = (s < ns && s_fin[s] == kStatusContinue) ? A.Y + (size_t)(b0 + s) * N : nullptr;
+        for (int i = tid; i < ldq; i += NT) {
+            ya[(size_t)i * S + s] = (y0 && i < N) ? y0[i] : 0.0f;
+            yb[(size_t)i * S + s] = 0.0f;
+        }
+    }
+    __syncthreads();
+    const SharedSolveCtl ctl = {s_h, s_fin, s_bad, s_new, s_Jp, s_Jd, s_jp, s_jd};
+    float* cur;
+    left = shared_converge_loop<S, true>(A, b0, ns, lds, ctl, A.Md + b0, A.Mp + b0, cur);
     if (left == 0) return;
     // the states still running: their iterate and resume words for the next launch
     for (int s = 0; s < ns; ++s) {

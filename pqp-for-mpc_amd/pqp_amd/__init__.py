@@ -119,6 +119,10 @@ SIGNATURES = {
     "pqp_shared_get": (C.c_int, [_vp, _fp, _fp, _fp, _fp, C.POINTER(C.c_int)]),
     "pqp_shared_relinearize": (C.c_int, [_vp, C.c_int] + [_vp] * 5 + [_vp]),
     "pqp_shared_solve": (C.c_int, [_vp, C.c_int] + [_vp] * 5 + [C.c_longlong] + [_vp] * 7 + [_vp]),
+    "pqp_shared_step_states": (C.c_int, [C.c_int] * 4),
+    "pqp_shared_create_plant": (C.c_int, [C.c_int] * 5 + [_fp] * 12 + [C.POINTER(C.c_void_p)]),
+    "pqp_shared_max_updates": (C.c_longlong, [_vp]),
+    "pqp_shared_step": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_longlong] + [_vp] * 10 + [_vp]),
     "pqp_rowblock_create": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, C.POINTER(C.c_void_p)]),
     "pqp_rowblock_update": (C.c_int, [_vp, _vp, _vp, _vp]),
     "pqp_rowblock_check": (C.c_int, [_vp, _vp]),
@@ -1191,6 +1195,102 @@ class SharedProblem:
             self.close()
         except Exception:
             pass
+
+
+class SharedPlant(SharedProblem):
+    """:class:`Plant` for the shapes past it (pqp_shared_create_plant /
+    pqp_shared_step of include/pqp.h, section 2i): one plant resident on the
+    device in :class:`SharedProblem`'s form plus its nine linear-term matrices,
+    and a control step of B states -- Fp, Mp, Fd, Md, then the converge solve,
+    cold or from the previous step's Y -- in ONE asynchronous launch.  Every
+    state's numbers are those of pqp_batch_compute_fp / _mp,
+    ``SharedProblem.relinearize`` and ``SharedProblem.solve``, bit for bit.
+    ``states`` is the number of states one workgroup takes (0: the library
+    refuses the shape, with the limit in its message), ``max_updates`` the
+    largest cap one step accepts.
+
+    ``arrays``: Plant.PLANT's, and optionally D (the disturbance ``step`` uses
+    when it is given none).  ``get``, ``relinearize`` and ``solve`` are
+    :class:`SharedProblem`'s, on the same handle (they share its output
+    tensors Y, U, h, status, Jp, Jd)."""
+
+    PLANT = Plant.PLANT
+    OUT = Plant.OUT
+
+    def __init__(self, N: int, M: int, nd: int, ns: int, device=None, **arrays):
+        import torch
+
+        self.torch = torch
+        self.N, self.M, self.nd, self.ns = int(N), int(M), int(nd), int(ns)
+        self._h = None
+        self.B = self._Bstep = 0  # states the output tensors / the step's own tensors are sized for
+        self.states = int(lib().pqp_shared_step_states(self.N, self.M, self.nd, self.ns))
+        sizes = dict(Qp_inv=M * M, Gp=N * M, Kp=N, Fp1=M * nd, Fp2=M * ns, Fp3=M, Mp1=ns * ns, Mp2=nd * ns,
+                     Mp3=nd * nd, Mp4=ns, Mp5=nd, Mp6=1)
+        host = {}
+        for k in self.PLANT:
+            if k not in arrays:
+                raise ValueError(f"SharedPlant: missing array {k}")
+            host[k] = _f32(arrays[k]).reshape(-1)
+            if self.states and host[k].size != sizes[k]:
+                raise ValueError(f"SharedPlant: {k} has {host[k].size} values, not {sizes[k]}")
+        self._D = _f32(arrays["D"]).reshape(-1) if arrays.get("D") is not None else None
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        h = C.c_void_p()
+        dev = self.device.index if self.device.index is not None else -1
+        _check(lib().pqp_shared_create_plant(dev, self.N, self.M, self.nd, self.ns, *[_buf(host[k]) for k in self.PLANT],
+                                             C.byref(h)))
+        self._h = h
+        self.max_updates = int(lib().pqp_shared_max_updates(h))
+        self._Dt = None
+
+    def _dev_step(self, a, cols: int, what: str):
+        torch = self.torch
+        if not torch.is_tensor(a):
+            a = np.ascontiguousarray(np.asarray(a, np.float32))
+        t = torch.as_tensor(a, dtype=torch.float32, device=self.device).reshape(-1, cols).contiguous()
+        if t.shape[0] != self._Bstep:
+            raise ValueError(f"SharedPlant.step: {what} must be [{self.B}, {cols}]")
+        return t
+
+    def step(self, x, D=None, Kp=None, warm: bool = False, floor: float | None = None, max_updates: int | None = None):
+        """One control step at states ``x`` [B, ns]: ``Plant.step``'s
+        arguments and meaning.  Fills the device tensors Y, U, h, status, Fp,
+        Mp, Fd, Md, Jp, Jd and returns self; one launch on torch's current
+        stream, no synchronisation."""
+        torch = self.torch
+        f = dict(dtype=torch.float32, device=self.device)
+        B = int(x.shape[0]) if hasattr(x, "shape") and len(x.shape) == 2 else len(x)
+        if B != self._Bstep or B != self.B:
+            if B <= 0:
+                _check(lib().pqp_shared_step(self._h, B, *([None] * 3), 0, 1, *([None] * 10), None))
+            self.B = self._Bstep = B
+            self.Y, self.U = torch.zeros(B, self.N, **f), torch.zeros(B, self.M, **f)
+            self.h = torch.zeros(B, dtype=torch.int64, device=self.device)
+            self.status = torch.zeros(B, dtype=torch.int32, device=self.device)
+            self.Fp, self.Fd = torch.zeros(B, self.M, **f), torch.zeros(B, self.N, **f)
+            self.Mp, self.Md, self.Jp, self.Jd = (torch.zeros(B, **f) for _ in range(4))
+            self._Dt = None
+        xt = self._dev_step(x, self.ns, "x")
+        if D is None:
+            if self._D is None:
+                raise ValueError("SharedPlant.step: this plant has no default D")
+            if self._Dt is None:
+                self._Dt = torch.as_tensor(np.tile(self._D, (B, 1)), **f).contiguous()
+            Dt = self._Dt
+        else:
+            Dt = self._dev_step(D, self.nd, "D")
+        Kt = None if Kp is None else self._dev_step(Kp, self.N, "Kp")
+        if floor is not None:
+            warm = True
+            self.Y.clamp_min_(float(floor))
+        p = ProblemBatch._p
+        cap = self.max_updates if max_updates is None else int(max_updates)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._inputs = (xt, Dt, Kt)  # alive until the next step: the launch is asynchronous
+        _check(lib().pqp_shared_step(self._h, B, p(xt), p(Dt), None if Kt is None else p(Kt), int(bool(warm)), cap,
+                                     *[p(getattr(self, k)) for k in self.OUT], stream))
+        return self
 
 
 def perturbed_states(x, B: int, seed: int = 5, rel: float = 0.05) -> np.ndarray:
