@@ -156,6 +156,90 @@ def test_fixed_mode_after_poison(gpu_lib, orc, N, M):
     assert_bitwise(f["Y"], Y, f"{N}/{M} fixed 9")
 
 
+# The shared-plant kernels (k_solve_shared, k_relin_shared, k_step_shared): LDS columns for the states a
+# ragged last block does not have (B = S + 1), padding rows past N and M, and in the step the solve's
+# vectors laid over the prologue's words.  Each case runs once as the suite left the LDS and once after NaN
+# was written over it: the same bits, and the oracle's (which have no NaN).
+def _unpoisoned_then_poisoned(gpu_lib, run, what):
+    first = run()
+    gpu_lib.poison_lds(float("nan"))
+    again = run()
+    for k in first:
+        assert np.array_equal(first[k].view(np.uint8), again[k].view(np.uint8)), f"{what}: {k} differs after poison"
+        if first[k].dtype == np.float32 and k not in ("Jp", "Jd"):
+            assert not np.isnan(again[k]).any(), f"{what}: NaN in {k}"
+    return again
+
+
+@pytest.mark.parametrize("shape", ["bundled", (1269, 8)], ids=["28x7", "1269x8"])
+def test_shared_solve_after_poison(gpu_lib, orc, shape):
+    from conftest import EXAMPLE_DIR
+    from test_gpu_shared_solve import check_state, feasible_copy, relin_and_solve, synthetic_states
+    from warm_ref import ref_solve_full
+
+    if shape == "bundled":
+        N, M, cap, Kp = 28, 7, 0, None
+        A = orc.load_example(EXAMPLE_DIR)
+        rng = np.random.default_rng(3)
+        B = gpu_lib.lib().pqp_shared_states(N, M) + 1
+        Ps = [orc.example_at_state(EXAMPLE_DIR, (A["x"] * (1.0 + 3.0 * rng.standard_normal(29))).astype(np.float32))
+              for _ in range(B)]
+        refs = Ps
+    else:
+        N, M = shape
+        cap = 4
+        B = gpu_lib.lib().pqp_shared_states(N, M) + 1
+        assert B == 5
+        A, Ps = synthetic_states(orc, N, M, B)
+        Kp = np.full((B, N), 1e30, np.float32)  # feasible: the costs and the fused update + Y'Qd pass
+        refs = [feasible_copy(P) for P in Ps]
+    with gpu_lib.SharedProblem(N, M, A["Qp_inv"], A["Gp"], A["Kp"]) as sp:
+        out = _unpoisoned_then_poisoned(gpu_lib, lambda: relin_and_solve(sp, Ps, Kp_solve=Kp, max_updates=cap),
+                                        f"shared solve ({N}, {M})")
+    for b in range(B):
+        want = ref_solve_full(orc, refs[b], np.full(N, 1000.0, np.float32), 0, max_updates=cap)
+        assert not np.isnan(want[4]) and not np.isnan(want[5])
+        check_state(out, b, want, f"({N}, {M}) after poison, state {b}")
+        assert not np.isnan(out["Jp"][b]) and not np.isnan(out["Jd"][b])
+
+
+@pytest.mark.parametrize("shape", [(28, 7, 1, 29), (28, 7, 3, 300)], ids=lambda s: "x".join(map(str, s)))
+def test_shared_step_after_poison(gpu_lib, orc, shape):
+    from plant_horizon_ref import check_state, host, plant_problem, synth_plant
+    from warm_ref import ref_solve_full
+
+    N, M, nd, ns = shape
+    B = gpu_lib.lib().pqp_shared_step_states(*shape) + 1
+    assert B > 2
+    A, states = synth_plant(orc, N, M, nd, ns, B)
+    x, D = states[0]
+    cap = 6
+    with gpu_lib.SharedPlant(N, M, nd, ns, **A) as sp:
+        out = _unpoisoned_then_poisoned(gpu_lib, lambda: host(sp.step(x, D=D, max_updates=cap)), f"step {shape}")
+    for b in range(B):
+        P = plant_problem(orc, A, N, M, nd, ns, x[b], D[b])
+        want = ref_solve_full(orc, P, np.full(N, 1000.0, np.float32), 0, max_updates=cap)
+        check_state(out, b, P, want, f"step {shape} after poison, state {b}")
+
+
+def test_shared_relinearize_after_poison(gpu_lib, orc):
+    from test_gpu_shared_solve import stack, synthetic_states
+
+    N, M = 40, 100
+    B = gpu_lib.lib().pqp_shared_states(N, M) + 1
+    A, Ps = synthetic_states(orc, N, M, B)
+    Fp, Mp = stack(Ps, "Fp"), stack(Ps, "Mp").reshape(-1)
+
+    def run():
+        Fd, Md = sp.relinearize(Fp, Mp)
+        return dict(Fd=Fd.cpu().numpy(), Md=Md.cpu().numpy())
+
+    with gpu_lib.SharedProblem(N, M, A["Qp_inv"], A["Gp"], A["Kp"]) as sp:
+        out = _unpoisoned_then_poisoned(gpu_lib, run, "relinearize (40, 100)")
+    assert_bitwise(out["Fd"].reshape(-1), stack(Ps, "Fd").reshape(-1), "relinearize after poison: Fd")
+    assert_bitwise(out["Md"], stack(Ps, "Md").reshape(-1), "relinearize after poison: Md")
+
+
 @pytest.mark.parametrize("tag", ["n1024_m512_s1_i0", "n1000_m500_s2_i7"])
 def test_batched_updates_after_poison(gpu_lib, golden_large, tag):
     """The headline batched update (k_batch_stream / the iterate kernels)."""

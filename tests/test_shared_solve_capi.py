@@ -82,6 +82,41 @@ def test_states_rule():
     assert L.pqp_shared_states(0, 8) == 0 and L.pqp_shared_states(8, 0) == 0 and L.pqp_shared_states(-1, -1) == 0
 
 
+SHAPE_TABLE = [((1264, 8), 8), ((1265, 8), 4), ((2536, 8), 4), ((2537, 8), 2), ((5084, 4), 2), ((5085, 4), 0),
+               ((12, 1030), 8)]
+
+
+@pytest.mark.parametrize("shape,S", SHAPE_TABLE, ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_states_at_the_thresholds(shape, S):
+    """The last shape of each S and the first of the next, by the 162816-byte budget (160 KiB less 1 KiB)
+    and solve_shared_state_floats; tests/test_gpu_shared_shapes.py launches every S on these grounds."""
+    import pqp_amd
+
+    N, M = shape
+    assert pqp_amd.lib().pqp_shared_states(N, M) == S
+    fits = [s for s in (8, 4, 2) if lds_bytes(N, M, s) <= 160 * KIB]
+    assert (fits[0] if fits else 0) == S  # the formula of DESIGN.md 4h agrees
+
+
+def test_step_states_of_the_tested_plant_shapes():
+    """Every plant shape test_gpu_shared_shapes.py steps takes the solve's S, also where the prologue's
+    words are the larger footprint."""
+    import pqp_amd
+    from test_gpu_shared_shapes import PROLOGUE_SIZED, SOLVE_CASES, STEP_CASES, STEP_SHAPES, r4
+
+    L = pqp_amd.lib()
+    for N, M, nd, ns in STEP_SHAPES:
+        S = L.pqp_shared_states(N, M)
+        assert S >= 2 and L.pqp_shared_step_states(N, M, nd, ns) == S, (N, M, nd, ns)
+        larger = 3 * r4(ns) + 2 * r4(nd) + 2 * r4(M) > 4 * r4(N) + 3 * r4(M)
+        assert larger == ((N, M, nd, ns) in PROLOGUE_SIZED), (N, M, nd, ns)
+    for shape, S, _, _ in STEP_CASES:
+        assert L.pqp_shared_states(*shape[:2]) == S, shape
+    for N, M, _, S, _ in SOLVE_CASES:  # and the solve's cases name the S they launch
+        assert L.pqp_shared_states(N, M) == S, (N, M)
+    assert {c[3] for c in SOLVE_CASES} == {8, 4, 2} == {c[1] for c in STEP_CASES}
+
+
 def test_states_sets_no_error():
     import pqp_amd
 
