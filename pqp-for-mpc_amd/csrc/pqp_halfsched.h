@@ -9,7 +9,9 @@
 // sum order of the other kernels), and wave I is at k-block K exactly when wave
 // K is at k-block I (I + K = T mod 16): tile (I, K) and its mirror (K, I) are
 // consumed in the same step, from one copy in LDS that the two waves load half
-// each.  Wave I reads it straight, wave K transposed.
+// each.  Wave I reads it straight, wave K transposed.  A diagonal tile (I, I) is
+// symmetric in itself: its wave loads three quarters of it and writes the
+// fourth from the mirror quadrant it holds.
 //
 // These functions are the schedule: the kernel calls them and restates none of
 // the arithmetic, and tests/halfsched/halfsched_check.cpp proves the hazards
@@ -30,7 +32,7 @@ namespace hs {
 
 constexpr int kWaves = 16;       // waves per workgroup = 64-row blocks of n_dual 1024
 constexpr int kTile = 64;        // tile edge (rows per wave, k per step)
-constexpr int kTileStride = 65;  // LDS words between two k of a tile: straight and transposed reads hit 64 banks
+constexpr int kTileStride = 66;  // LDS words between two k of a tile: even, so that a row of k starts on 8 bytes
 constexpr int kTileWords = kTile * kTileStride;
 constexpr int kSlots = 9;        // tiles in LDS per step: at most 7 pairs + 2 diagonal
 constexpr int kHalfCols = 32;    // k columns of a tile in one half
@@ -72,7 +74,8 @@ PQP_HS_HD bool diagonal(int T, int wave) { return partner(T, wave) == wave; }
 
 // Which halves of the tile (bit 0: k columns 0..31, bit 1: 32..63) this wave
 // loads for step T: the lower wave of a pair the first, the higher one the
-// second, a self-paired wave both.
+// second, a self-paired wave both -- of the second only the quadrant below the
+// diagonal (rows 32..63, quad_*() below): 3/4 of the tile's bytes.
 PQP_HS_HD int load_halves(int T, int wave, int C) {
     if (!active(T, wave, C)) return 0;
     const int p = partner(T, wave);
@@ -81,6 +84,42 @@ PQP_HS_HD int load_halves(int T, int wave, int C) {
 
 // first k column of the first (or only) half in a load_halves() mask
 PQP_HS_HD int first_half_col(int halves) { return (halves & 1) ? 0 : kHalfCols; }
+
+// The tile in LDS and the lanes' pieces of it.  Entry (i, k) of a tile sits at
+// word k * 66 + i of its slot (words 64 and 65 of a row of k are padding that
+// nothing reads or writes).
+//  - The straight read (lane = i, the lower wave and a diagonal wave) takes
+//    word k * 66 + lane: 64 consecutive words per ds_read_b32.
+//  - The transposed read (lane = k, the higher wave: Qd(k, i) for Qd(i, k))
+//    takes the 8-byte pair i, i + 1 at lane * 66 + i with one ds_read_b64; rows
+//    start 66 = 2 mod 64 words apart, so the 32 lanes of a lane group cover 64
+//    banks.
+//  - A piece is what one 16-byte load brings: rows r .. r + 3 of one k.  It goes
+//    to LDS as two ds_write_b64, which are served in groups of 16 consecutive
+//    lanes on 32 banks: lane bits 0-2 and 4 choose the row group, bits 3 and 5
+//    the k, so a group of 16 lanes holds 8 adjacent row groups (banks 4 g,
+//    4 g + 1 or 4 g + 2, 4 g + 3) at two adjacent k, and the odd k, 66 words on,
+//    falls into the banks the even one leaves free.  A half has 8 loads per
+//    lane, load j at k piece_col(lane) + 4 j of the half: every load
+//    instruction still reads whole k of 256 bytes.
+//  - The quadrant of a diagonal tile (rows 32..63, k 32..63) has 4 loads per
+//    lane: lane bits 0-2 choose the row group, bits 3-5 the k, load j at k
+//    quad_col(lane) + 8 j: whole 128-byte runs, and the same 16-lane groups.
+//  - The quadrant above the diagonal (rows 0..31, k 32..63) is never loaded.
+//    The lanes whose pieces of the first half lie in rows 32..63 (mirrors())
+//    store each value Q(r, c) a second time at (row c, k r), one ds_write_b32
+//    each: by the caller's contract these are the bits of Q(c, r).
+// tests/halfsched/half_layout_check.cpp checks coverage, alignment and bank
+// conflicts on these functions.
+constexpr int kPieceRows = 4;   // rows of one 16-byte load
+constexpr int kHalfLoads = 8;   // loads per lane for one half
+constexpr int kQuadLoads = 4;   // loads per lane for a diagonal tile's quadrant
+PQP_HS_HD int tile_word(int i, int k) { return k * kTileStride + i; }
+PQP_HS_HD int piece_row(int lane) { return kPieceRows * ((lane & 7) | ((lane >> 1) & 8)); }
+PQP_HS_HD int piece_col(int lane) { return ((lane >> 3) & 1) | ((lane >> 4) & 2); }  // + 4 j within the half
+PQP_HS_HD int quad_row(int lane) { return kHalfCols + kPieceRows * (lane & 7); }
+PQP_HS_HD int quad_col(int lane) { return kHalfCols + (lane >> 3); }  // + 8 j
+PQP_HS_HD bool mirrors(int lane) { return piece_row(lane) >= kHalfCols; }
 
 // LDS slot (0 .. kSlots - 1) of the pair's tile at step T.  With t = T mod 16
 // the pairs have I + K = t (lower wave 0 .. t/2) or t + 16 (lower wave t + 1 ..

@@ -454,10 +454,11 @@ __global__ void __launch_bounds__(256) k_batch_resident(const float* __restrict_
 // per problem, wave I owning rows 64 I .. 64 I + 63 (one row per lane), on the
 // skewed schedule of pqp_halfsched.h: at step T wave I sums k-block K = (T - I)
 // mod 16 while wave K sums k-block I, both from one copy of tile (min, max) in
-// LDS that each of them loaded half of (a wave on a diagonal tile loads all of
-// its own).  Rows of stride 65 words make the straight read (the lower wave)
-// and the transposed one (the higher wave, Qd(k, i) for Qd(i, k)) free of bank
-// conflicts.  Per step: the half-tile prefetched in registers goes to LDS,
+// LDS that each of them loaded half of (a wave on a diagonal tile loads three
+// quarters of its own and writes the fourth from its mirror).  Rows of stride
+// 66 words make the straight read (the lower wave, 4 bytes per lane) and the
+// transposed one (the higher wave, Qd(k, i) for Qd(i, k), 8 bytes per lane)
+// free of bank conflicts, and the stores 8 bytes wide.  Per step: the half-tile prefetched in registers goes to LDS,
 // barrier, the next step's loads are issued, 64 k are summed with y broadcast
 // from LDS, and a wave past its k-block 15 applies the update into the other y
 // buffer; barrier.  Every row adds lean4's / literal1's terms in k = 0 .. N-1
@@ -473,6 +474,25 @@ __device__ __forceinline__ void lean1(float& ap, float& an, float q, float y) {
     ap += (q < 0.0f) ? z : p;
     an += (q > 0.0f) ? z : -p;
 }
+// CH consecutive k of this lane's row of a tile, the first at q, k apart by SK words: SK = 1 is the transposed
+// read, whose row starts on 8 bytes (pqp_halfsched.h), as explicit 8-byte loads
+// (volatile keeps each a ds_read_b64: merged into ds_read2_b64 a pair is served at half the rate; the pointer
+// names the LDS address space, which is not inferred for a volatile access)
+typedef float hf2 __attribute__((ext_vector_type(2)));
+typedef volatile hf2 __attribute__((address_space(3))) lds_hf2;
+template <int SK, int CH>
+__device__ __forceinline__ void half_tile_entries(float (&qv)[CH], const float* __restrict__ q) {
+    if constexpr (SK == 1) {
+#pragma unroll
+        for (int j = 0; j < CH; j += 2) {
+            const hf2 v = *(const lds_hf2*)(q + j);
+            qv[j] = v.x, qv[j + 1] = v.y;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < CH; ++j) qv[j] = q[j * SK];
+    }
+}
 // 64 k of one tile in LDS for this lane's row: entry k at q[k * SK]; DIAG: the
 // tile holds the row's diagonal entry (k == lane): literal form with theta
 // there, as in the diagonal window of the other kernels (off the diagonal the
@@ -480,14 +500,13 @@ __device__ __forceinline__ void lean1(float& ap, float& an, float q, float y) {
 template <int SK, bool DIAG>
 __device__ __forceinline__ void half_tile_sum(float& ap, float& an, const float* __restrict__ q,
                                               const float* __restrict__ yk, int lane, float th) {
-    // 8 k per pass: with 16 the two prefetch buffers no longer fit beside it in
-    // the 128 registers of a 16-wave workgroup (14 spilled)
+    // 8 k per pass: 16 do not fit in the 128 registers of a 16-wave workgroup even beside a
+    // prefetch buffer of 8 + 4 loads (128 VGPRs and 12 bytes of scratch; 112 / 114 VGPRs with 8)
     constexpr int CH = 8;
 #pragma unroll 1
     for (int c = 0; c < hs::kTile; c += CH) {
         float qv[CH];
-#pragma unroll
-        for (int j = 0; j < CH; ++j) qv[j] = q[(c + j) * SK];
+        half_tile_entries<SK, CH>(qv, q + c * SK);
 #pragma unroll
         for (int j = 0; j < CH; j += 4) {
             const float4 yv = *reinterpret_cast<const float4*>(yk + c + j);
@@ -513,7 +532,6 @@ __device__ __forceinline__ void half_tile_sum(float& ap, float& an, const float*
 // the sums start at +0 and never reach -0, so x + (-0) == x + (+0) for every x
 // they hold (tests/halfsched/half_pf_check.cpp walks the special values).  The
 // kernel decides both conditions itself, per wave and step.
-typedef float hf2 __attribute__((ext_vector_type(2)));
 template <int SK>
 __device__ __forceinline__ void half_tile_sum_pf(float& ap, float& an, const float* __restrict__ q,
                                                  const float* __restrict__ yk) {
@@ -524,8 +542,7 @@ __device__ __forceinline__ void half_tile_sum_pf(float& ap, float& an, const flo
 #pragma unroll 1
     for (int c = 0; c < hs::kTile; c += CH) {
         float qv[CH];
-#pragma unroll
-        for (int j = 0; j < CH; ++j) qv[j] = q[(c + j) * SK];
+        half_tile_entries<SK, CH>(qv, q + c * SK);
 #pragma unroll
         for (int j = 0; j < CH; j += 4) {
             const float4 yv = *reinterpret_cast<const float4*>(yk + c + j);
@@ -553,6 +570,12 @@ __device__ __forceinline__ int half_y_flag(float y) {
 __device__ __forceinline__ float half_q_fold(float s, f32x4 q) {
     return hs::q_fold(hs::q_fold(hs::q_fold(hs::q_fold(s, q.x), q.y), q.z), q.w);
 }
+// one piece (4 rows of one k) into its tile: two 8-byte stores, which pqp_halfsched.h's lane map keeps free of
+// bank conflicts (d is 8-byte aligned: an even row of an even stride; volatile keeps them two ds_write_b64)
+__device__ __forceinline__ void half_store_piece(float* d, f32x4 v) {
+    *(lds_hf2*)d = hf2{v.x, v.y};
+    *(lds_hf2*)(d + 2) = hf2{v.z, v.w};
+}
 // LDS: the y ping-pong, the tile slots, then the flag words (pqp_halfsched.h)
 constexpr size_t kHalfLdsBytes =
     ((size_t)2 * 1024 + (size_t)hs::kSlots * hs::kTileWords + hs::kFlagWords) * sizeof(float);
@@ -564,7 +587,7 @@ __global__ void __launch_bounds__(1024) k_batch_half(const float* __restrict__ Q
                                                      const float* __restrict__ theta, const float* __restrict__ Fd,
                                                      int ldv, const float* Y0, float* Y, int updates) {
     constexpr int N = 1024;
-    constexpr int HL = hs::kHalfCols / 4;  // 16-byte loads per lane and half: one covers 4 rows of one k
+    constexpr int HL = hs::kHalfLoads, QL = hs::kQuadLoads;  // 16-byte loads per lane: one covers 4 rows of one k
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* ybuf = lds;           // [2][N]: update h reads hs::y_read_buf(h), writes the other
     float* tiles = lds + 2 * N;  // [hs::kSlots][hs::kTileWords]
@@ -584,33 +607,35 @@ __global__ void __launch_bounds__(1024) k_batch_half(const float* __restrict__ Q
     }
     const float th = theta[(size_t)b * ldv + row];
     const float f = Fd[(size_t)b * ldv + row];
-    // this lane's part of a tile: rows lr .. lr + 3 of k lk, lk + 4, ...
-    const int lk = lane >> 4, lr = 4 * (lane & 15);
-    f32x4 pa[HL], pb[HL];  // pa: this wave's half (the first of a diagonal tile), pb: a diagonal tile's second
+    // this lane's pieces of a tile (pqp_halfsched.h): rows lr .. lr + 3 of k lk, lk + 4, ... of a half, rows
+    // qr .. qr + 3 of k qk, qk + 8, ... of a diagonal tile's quadrant
+    const int lk = hs::piece_col(lane), lr = hs::piece_row(lane);
+    const int qk = hs::quad_col(lane), qr = hs::quad_row(lane);
+    f32x4 pa[HL], pb[QL];  // pa: this wave's half (the first of a diagonal tile), pb: a diagonal tile's quadrant
     auto issue = [&](int T) {  // step T's loads (non-temporal: every tile is read once per update)
         const int halves = hs::load_halves(T, wave, updates);
         if (halves == 0) return;
-        const int k0 = hs::kTile * hs::tile_cols(T, wave) + hs::first_half_col(halves) + lk;
-        const float* src = Q + (size_t)k0 * ldq + hs::kTile * hs::tile_rows(T, wave) + lr;
+        const float* tile0 = Q + (size_t)(hs::kTile * hs::tile_cols(T, wave)) * ldq + hs::kTile * hs::tile_rows(T, wave);
+        const float* src = tile0 + (size_t)(hs::first_half_col(halves) + lk) * ldq + lr;
 #pragma unroll
         for (int j = 0; j < HL; ++j)
             pa[j] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src + (size_t)(4 * j) * ldq));
         if (halves == 3) {
+            const float* qsrc = tile0 + (size_t)qk * ldq + qr;
 #pragma unroll
-            for (int j = 0; j < HL; ++j)
-                pb[j] = __builtin_nontemporal_load(
-                    reinterpret_cast<const f32x4*>(src + (size_t)(hs::kHalfCols + 4 * j) * ldq));
+            for (int j = 0; j < QL; ++j)
+                pb[j] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(qsrc + (size_t)(8 * j) * ldq));
         }
     };
-    auto stash = [&](int T) {  // the loaded halves into the pair's slot, entry (i, k) at k * 65 + i
+    auto stash = [&](int T) {  // what was loaded into the pair's slot, entry (i, k) at hs::tile_word(i, k)
         const int halves = hs::load_halves(T, wave, updates);
         if (halves == 0) return;
-        float* dst = tiles + hs::slot(T, wave) * hs::kTileWords + (hs::first_half_col(halves) + lk) * hs::kTileStride + lr;
+        float* tile = tiles + hs::slot(T, wave) * hs::kTileWords;
+        float* dst = tile + hs::tile_word(lr, hs::first_half_col(halves) + lk);
         float fold = 0.0f;
 #pragma unroll
         for (int j = 0; j < HL; ++j) {
-            float* d = dst + 4 * j * hs::kTileStride;
-            d[0] = pa[j].x, d[1] = pa[j].y, d[2] = pa[j].z, d[3] = pa[j].w;
+            half_store_piece(dst + 4 * j * hs::kTileStride, pa[j]);
             if constexpr (PF) fold = half_q_fold(fold, pa[j]);
         }
         if constexpr (PF) {  // a diagonal tile is summed in the literal form whatever it holds
@@ -619,10 +644,18 @@ __global__ void __launch_bounds__(1024) k_batch_half(const float* __restrict__ Q
                     __builtin_amdgcn_ballot_w64(hs::q_dirty(fold)) != 0;
         }
         if (halves == 3) {
+            float* qdst = tile + hs::tile_word(qr, qk);
 #pragma unroll
-            for (int j = 0; j < HL; ++j) {
-                float* d = dst + (hs::kHalfCols + 4 * j) * hs::kTileStride;
-                d[0] = pb[j].x, d[1] = pb[j].y, d[2] = pb[j].z, d[3] = pb[j].w;
+            for (int j = 0; j < QL; ++j) half_store_piece(qdst + 8 * j * hs::kTileStride, pb[j]);
+            // the quadrant above the diagonal, from its mirror: Q(lr + m, k) once more at (row k, k lr + m)
+            if (hs::mirrors(lane)) {
+                float* mdst = tile + hs::tile_word(lk, lr);
+#pragma unroll
+                for (int j = 0; j < HL; ++j) {
+                    float* d = mdst + 4 * j;
+                    d[0] = pa[j].x, d[hs::kTileStride] = pa[j].y, d[2 * hs::kTileStride] = pa[j].z,
+                    d[3 * hs::kTileStride] = pa[j].w;
+                }
             }
         }
     };
@@ -650,10 +683,10 @@ __global__ void __launch_bounds__(1024) k_batch_half(const float* __restrict__ Q
                                       flags[hs::y_flag(hs::y_read_buf(h), K)];
                     fast = __builtin_amdgcn_readfirstlane(dirty) == 0;
                 }
-                if (hs::transposed(T, wave)) {  // row * 65 + k
+                if (hs::transposed(T, wave)) {  // row * 66 + k
                     if (fast) half_tile_sum_pf<1>(ap, an, tile + lane * hs::kTileStride, yk);
                     else half_tile_sum<1, false>(ap, an, tile + lane * hs::kTileStride, yk, lane, th);
-                } else {  // k * 65 + row
+                } else {  // k * 66 + row
                     if (fast) half_tile_sum_pf<hs::kTileStride>(ap, an, tile + lane, yk);
                     else half_tile_sum<hs::kTileStride, false>(ap, an, tile + lane, yk, lane, th);
                 }
