@@ -710,6 +710,76 @@ int pqp_shared_step(pqp_shared *p, int B, const float *d_x, const float *d_D, co
                     long long max_updates, float *d_Y, float *d_U, long long *d_h, int *d_status,
                     float *d_Fp, float *d_Mp, float *d_Fd, float *d_Md, float *d_Jp, float *d_Jd, void *stream);
 
+/* ----------------------------------------------------------------------
+ * 2j. The closed loop: K control steps of B plant states in one call.
+ * 2e to 2i solve the step; what takes a state to the next sample time is the
+ * plant's own dynamics x+ = A x + Bu U + Bd D.  A pqp_dynamics keeps A, Bu and
+ * Bd on its device; pqp_dynamics_advance takes B states one sample time
+ * forward in one launch, and pqp_plant_rollout runs K steps of B states of a
+ * pqp_plant -- step, state update, warm step, ... -- without leaving the
+ * device: for the one-wave plants of 2f in ONE launch, in which a wave carries
+ * its state through all K steps with Y, x and the plant in LDS; for the
+ * one-workgroup plants of 2g (and for 2f's under the tuning key
+ * plant_roll_chain = 1) as a chain of 2 K launches, k_plant_step or
+ * k_plant_step_mid then k_plant_advance, K times (one more launch, the floor,
+ * when warm != 0 and y_floor > 0), with no host work in between.
+ *
+ * The state update is the reference's own primitives, three matrixMultiply
+ * (PQP_CPU.c:84) and two matrixAdd (:157): t = A x, v = Bu U, w = Bd D, every
+ * sum from +0.0f in index order, every product rounded before its add (no
+ * FMA); x+ = (t + 1.0f * v) + 1.0f * w.  Bu acts on the whole U and Bd on the
+ * whole D: no stage ordering is assumed.
+ *
+ * Bit-exactness of the rollout: step k of state b gives exactly what
+ * pqp_plant_step gives at x = X[k][b], the D of step k, d_Kp[b] and the same
+ * cap -- Y, U, h, status, Jp, Jd, NaN rules included -- started warm whenever
+ * k > 0 and as `warm` says at k = 0; before every warm start each entry of Y
+ * is replaced by y_floor > Y_i ? y_floor : Y_i when y_floor > 0 (y_floor <= 0:
+ * Y is taken as given, as in 2e).  X[k + 1][b] is the state update of X[k][b]
+ * with the step's U, whatever its status.  The fused launch and the chain give
+ * the same bits.
+ *
+ * pqp_plant_rollout's contract is pqp_plant_step's, word for word:
+ * asynchronous on `stream`, no allocation, no synchronisation, no copy to the
+ * host, the caller's device restored, so it can be captured in a graph; it
+ * works on both kinds of pqp_plant.  Every argument error is PQP_ERR_ARG
+ * before any device is looked for.
+ * -------------------------------------------------------------------- */
+typedef struct pqp_dynamics pqp_dynamics;
+
+/* Host pointers, row-major: A [ns*ns], Bu [ns*M], Bd [ns*nd].  1 <= ns, nd <= 64, 1 <= M <= 1024
+ * (every M of a pqp_plant or a pqp_shared), else PQP_ERR_ARG.  device -1: the current one.
+ * Synchronous.  Immutable after create and bound to its device. */
+int pqp_dynamics_create(int device, int ns, int M, int nd, const float *A, const float *Bu, const float *Bd,
+                        pqp_dynamics **out);
+int pqp_dynamics_destroy(pqp_dynamics *d);
+
+/* d_xnext [B][ns] = the state update of d_x [B][ns] with d_U [B][M] and d_D [B][nd].  ONE launch on
+ * `stream`, asynchronous, no allocation, no synchronisation; runs on the handle's device and restores
+ * the caller's.  d_xnext must not overlap d_x (PQP_ERR_ARG).  The chain's building block; with
+ * pqp_shared_step in a graph it closes the shared plant's loop (2i). */
+int pqp_dynamics_advance(const pqp_dynamics *d, int B, const float *d_x, const float *d_U, const float *d_D,
+                         float *d_xnext, void *stream);
+
+/* 1 when pqp_plant_rollout of that shape is a single launch at default tuning: kind 1 (2f's
+ * shapes) with the dynamics within the launch's LDS beside the plant, which holds for every such
+ * shape today.  0 when it is the chain (kind 2) or the shape is no plant's.  No device needed, no
+ * error set.  (A plant made on a device where that launch has no occupancy takes the chain.) */
+int pqp_plant_rollout_fused(int N, int M, int nd, int ns);
+
+/* K steps of B states.
+ * In:  d_X [K+1][B][ns]: row 0 the states, never written; rows 1..K are outputs.
+ *      d_D [B][nd], used at every step (D_steps == 1), or [K][B][nd] (D_steps == K); any other
+ *      D_steps: PQP_ERR_ARG.  d_Kp NULL or [B][N], constant over the steps.  warm, y_floor: above.
+ *      1 <= max_updates <= pqp_plant_max_updates(p), per step.  dyn: the plant's ns, M, nd, on
+ *      the plant's device.
+ * Out: d_Y [B][N], in/out: it ends as step K-1's Y (not floored).  d_U [K][B][M].  d_h, d_status,
+ *      d_Jp, d_Jd [K][B], each optional (NULL: not written). */
+int pqp_plant_rollout(pqp_plant *p, const pqp_dynamics *dyn, int B, int K, float *d_X, const float *d_D,
+                      int D_steps, const float *d_Kp, int warm, float y_floor, long long max_updates,
+                      float *d_Y, float *d_U, long long *d_h, int *d_status, float *d_Jp, float *d_Jd,
+                      void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -122,6 +122,9 @@ extern "C" {
  *   plant_pipe [0]         pqp_plant_step's iteration: 0 plain, 1 software-pipelined
  *                          (k_solve_wave's two forms); ignored by the one-workgroup
  *                          step of pqp.h 2g
+ *   plant_roll_chain [0]   pqp_plant_rollout of a one-wave plant: 0 the fused
+ *                          launch, 1 the chain of step and advance launches that
+ *                          the one-workgroup plants always take (same bits)
  *  Paths and failure tests:
  *   persist_off [0]        fixed mode of n_dual <= 1024 through the graph-replayed
  *                          relay instead of the persistent launch

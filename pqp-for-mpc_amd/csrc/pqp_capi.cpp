@@ -425,6 +425,16 @@ struct pqp_plant {
     pqp::DevBuf Qinv, Gp, Kp, Qp, Qd, GQ, theta;
     pqp::DevBuf Fp1, Fp2, Fp3, Mp1, Mp2, Mp3, Mp4, Mp5, Mp6;
     pqp::PlantData data{};
+    int roll_slots = 0;      // kind 1: workgroups of the fused rollout resident at once (0: the rollout is the chain)
+};
+
+// A plant's state update x+ = (A x + Bu U) + Bd D resident on its device (pqp_dynamics_*, 2j): the three
+// matrices transposed, as k_plant_advance and the fused rollout read them.  Immutable after create.
+struct pqp_dynamics {
+    int ns = 0, M = 0, nd = 0;
+    int dev = -1;  // the device it was made on (its calls run there)
+    pqp::DevBuf AT, BuT, BdT;
+    pqp::DynData data{};
 };
 
 // One plant's shared data for the shared-plant converge solve (pqp_shared_*, 2h): the primal data as
@@ -1156,7 +1166,7 @@ using namespace pqp;
 
 extern "C" {
 
-int pqp_version(void) { return 112; }  // ABI revision: INTEGRATION.md section 6
+int pqp_version(void) { return 113; }  // ABI revision: INTEGRATION.md section 6
 
 // ---------------------------------------------------------------------------
 // 2a. status-returning host API
@@ -2080,6 +2090,13 @@ static int plant_create(const char* fn, bool horizon, int device, int N, int M, 
                              hipGetErrorString(e));
         }
     }
+    if (kind == 1 && plant_roll_shape_ok(N, M, nd, ns)) {  // 2j: the fused rollout's grid bound
+        P->roll_slots = plant_roll_resident_wgs(N, M, nd, ns);
+        if (P->roll_slots <= 0) {  // a plant that steps is made as before: its rollout is then the chain
+            (void)hipGetLastError();
+            P->roll_slots = 0;
+        }
+    }
     if (kind == 2) {
         // what k_solve_mid2 finds in Qd when it stages a problem, once: bit symmetry by the batched
         // entry points' kernel, NaN / inf by a scan of the host copy
@@ -2151,6 +2168,19 @@ long long pqp_plant_max_updates(const pqp_plant* p) {
     return pqp::batch_chunk_for(p->N, p->M);
 }
 
+// One step's launch on the plant's device (current): the kind's kernel, at the tuning knobs' form.
+static int plant_launch_step(const pqp_plant& p, const PlantStep& S, hipStream_t s) {
+    if (p.kind == 2) {  // the one-workgroup step: plant_pipe has no meaning for it
+        PlantMidFlags F = p.mid;
+        F.dense = g_tune.mid2_dense ? 1 : 0;
+        PQP_HIP(launch_plant_step_mid(p.data, S, F, p.slots[0], s));
+        return PQP_OK;
+    }
+    const bool pipe = g_plant_pipe != 0;
+    PQP_HIP(launch_plant_step(p.data, S, p.slots[pipe ? 1 : 0], pipe, s));
+    return PQP_OK;
+}
+
 int pqp_plant_step(pqp_plant* p, int B, const float* d_x, const float* d_D, const float* d_Kp, int warm,
                    long long max_updates, float* d_Y, float* d_U, long long* d_h, int* d_status, float* d_Fp,
                    float* d_Mp, float* d_Fd, float* d_Md, float* d_Jp, float* d_Jd, void* stream) {
@@ -2168,15 +2198,128 @@ int pqp_plant_step(pqp_plant* p, int B, const float* d_x, const float* d_D, cons
     S.x = d_x, S.D = d_D, S.Kp = d_Kp;
     S.Y = d_Y, S.U = d_U, S.h = d_h, S.status = d_status;
     S.Fp = d_Fp, S.Mp = d_Mp, S.Fd = d_Fd, S.Md = d_Md, S.Jp = d_Jp, S.Jd = d_Jd;
-    const bool pipe = g_plant_pipe != 0;
     DeviceGuard on(p->dev);
-    if (p->kind == 2) {  // the one-workgroup step: plant_pipe has no meaning for it
-        PlantMidFlags F = p->mid;
-        F.dense = g_tune.mid2_dense ? 1 : 0;
-        PQP_HIP(launch_plant_step_mid(p->data, S, F, p->slots[0], static_cast<hipStream_t>(stream)));
+    return plant_launch_step(*p, S, static_cast<hipStream_t>(stream));
+}
+
+// ---------------------------------------------------------------------------
+// 2j. the closed loop: the plant's dynamics, and K control steps in one call
+// ---------------------------------------------------------------------------
+int pqp_dynamics_create(int device, int ns, int M, int nd, const float* A, const float* Bu, const float* Bd,
+                        pqp_dynamics** out) {
+    if (!out) return set_error(PQP_ERR_ARG, "pqp_dynamics_create: null handle pointer");
+    *out = nullptr;
+    if (ns < 1 || ns > 64 || nd < 1 || nd > 64 || M < 1 || M > kDynMaxM)
+        return set_error(PQP_ERR_ARG, "pqp_dynamics_create: (ns=%d, M=%d, nd=%d) is outside 1 <= ns, nd <= 64, "
+                                      "1 <= M <= %d", ns, M, nd, kDynMaxM);
+    if (!A || !Bu || !Bd) return set_error(PQP_ERR_ARG, "pqp_dynamics_create: null input");
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return set_error(PQP_ERR_NO_DEVICE, "libpqp: no HIP device visible");
+    if (device < 0 && hipGetDevice(&device) != hipSuccess)
+        return set_error(PQP_ERR_NO_DEVICE, "libpqp: cannot query the current device");
+    if (device >= n) return set_error(PQP_ERR_ARG, "pqp_dynamics_create: device %d of %d", device, n);
+    DeviceGuard on(device);
+    PQP_TRY(ensure_device());
+    hipStream_t s = lib_stream();
+    std::unique_ptr<pqp_dynamics> D(new pqp_dynamics());
+    D->ns = ns, D->M = M, D->nd = nd;
+    D->dev = device;
+    // k-major copies: word [k][i] is the reference's [i][k]
+    auto transposed = [ns](const float* a, int cols) {
+        std::vector<float> t((size_t)cols * ns);
+        for (int i = 0; i < ns; ++i)
+            for (int k = 0; k < cols; ++k) t[(size_t)k * ns + i] = a[(size_t)i * cols + k];
+        return t;
+    };
+    const std::vector<float> at = transposed(A, ns), but = transposed(Bu, M), bdt = transposed(Bd, nd);
+    PQP_TRY(upload(D->AT, at.data(), at.size(), s));
+    PQP_TRY(upload(D->BuT, but.data(), but.size(), s));
+    PQP_TRY(upload(D->BdT, bdt.data(), bdt.size(), s));
+    PQP_HIP(hipStreamSynchronize(s));  // the host copies are free after it
+    D->data = DynData{ns, M, nd, D->AT.f(), D->BuT.f(), D->BdT.f()};
+    *out = D.release();
+    return PQP_OK;
+}
+
+int pqp_dynamics_destroy(pqp_dynamics* d) {
+    if (!d) return PQP_OK;
+    DeviceGuard on(d->dev);
+    delete d;
+    return PQP_OK;
+}
+
+int pqp_dynamics_advance(const pqp_dynamics* d, int B, const float* d_x, const float* d_U, const float* d_D,
+                         float* d_xnext, void* stream) {
+    if (!d) return set_error(PQP_ERR_ARG, "pqp_dynamics_advance: null dynamics");
+    if (B <= 0) return set_error(PQP_ERR_ARG, "pqp_dynamics_advance: B = %d states", B);
+    if (!d_x || !d_U || !d_D || !d_xnext)
+        return set_error(PQP_ERR_ARG, "pqp_dynamics_advance: null d_x, d_U, d_D or d_xnext");
+    if (d_xnext == d_x) return set_error(PQP_ERR_ARG, "pqp_dynamics_advance: d_xnext aliases d_x");
+    const size_t words = (size_t)B * d->ns;
+    if (d_xnext < d_x + words && d_x < d_xnext + words)
+        return set_error(PQP_ERR_ARG, "pqp_dynamics_advance: d_xnext overlaps d_x");
+    DeviceGuard on(d->dev);
+    PlantAdvance a{B, 0, 0.0f, d_x, d_U, d_D, d_xnext, nullptr};
+    PQP_HIP(launch_plant_advance(d->data, a, static_cast<hipStream_t>(stream)));
+    return PQP_OK;
+}
+
+int pqp_plant_rollout_fused(int N, int M, int nd, int ns) { return plant_roll_shape_ok(N, M, nd, ns) ? 1 : 0; }
+
+int pqp_plant_rollout(pqp_plant* p, const pqp_dynamics* dyn, int B, int K, float* d_X, const float* d_D, int D_steps,
+                      const float* d_Kp, int warm, float y_floor, long long max_updates, float* d_Y, float* d_U,
+                      long long* d_h, int* d_status, float* d_Jp, float* d_Jd, void* stream) {
+    if (!p) return set_error(PQP_ERR_ARG, "pqp_plant_rollout: null plant");
+    if (!dyn) return set_error(PQP_ERR_ARG, "pqp_plant_rollout: null dynamics");
+    if (B <= 0) return set_error(PQP_ERR_ARG, "pqp_plant_rollout: B = %d states", B);
+    if (K <= 0) return set_error(PQP_ERR_ARG, "pqp_plant_rollout: K = %d steps", K);
+    if (D_steps != 1 && D_steps != K)
+        return set_error(PQP_ERR_ARG, "pqp_plant_rollout: D_steps = %d is neither 1 nor K = %d", D_steps, K);
+    if (!d_X || !d_D || !d_Y || !d_U) return set_error(PQP_ERR_ARG, "pqp_plant_rollout: null d_X, d_D, d_Y or d_U");
+    const long long cap = pqp::batch_chunk_for(p->N, p->M);
+    if (max_updates < 1 || max_updates > cap)
+        return set_error(PQP_ERR_ARG, "pqp_plant_rollout: max_updates = %lld is outside 1 .. %lld (pqp_plant_max_updates: "
+                                      "one step's budget)", max_updates, cap);
+    if (dyn->ns != p->ns || dyn->M != p->M || dyn->nd != p->nd)
+        return set_error(PQP_ERR_ARG, "pqp_plant_rollout: the dynamics' (ns=%d, M=%d, nd=%d) are not the plant's "
+                                      "(ns=%d, M=%d, nd=%d)", dyn->ns, dyn->M, dyn->nd, p->ns, p->M, p->nd);
+    if (dyn->dev != p->dev)
+        return set_error(PQP_ERR_ARG, "pqp_plant_rollout: the dynamics are on device %d, the plant on device %d", dyn->dev,
+                         p->dev);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t B_ = (size_t)B;
+    PlantStep S{};
+    S.B = B;
+    S.max_updates = max_updates;
+    S.Kp = d_Kp;
+    S.Y = d_Y;
+    DeviceGuard on(p->dev);
+    if (p->kind == 1 && p->roll_slots > 0 && !g_plant_roll_chain) {  // ONE launch: k_plant_step's ROLL form
+        S.warm = warm ? 1 : 0;
+        S.D = d_D;
+        S.U = d_U, S.h = d_h, S.status = d_status, S.Jp = d_Jp, S.Jd = d_Jd;
+        const PlantRoll R{K, D_steps, y_floor, d_X, dyn->data};
+        PQP_HIP(launch_plant_roll(p->data, S, R, p->roll_slots, s));
         return PQP_OK;
     }
-    PQP_HIP(launch_plant_step(p->data, S, p->slots[pipe ? 1 : 0], pipe, static_cast<hipStream_t>(stream)));
+    // the chain: K times the step and the advance, which also floors Y for the next step
+    const bool floored = y_floor > 0.0f;
+    if (warm && floored) PQP_HIP(launch_plant_floor(d_Y, B_ * p->N, y_floor, s));
+    for (int k = 0; k < K; ++k) {
+        const size_t kb = (size_t)k * B_;
+        S.warm = (k > 0 || warm) ? 1 : 0;
+        S.x = d_X + kb * p->ns;
+        S.D = d_D + (D_steps > 1 ? kb * p->nd : (size_t)0);
+        S.U = d_U + kb * p->M;
+        S.h = d_h ? d_h + kb : nullptr;
+        S.status = d_status ? d_status + kb : nullptr;
+        S.Jp = d_Jp ? d_Jp + kb : nullptr;
+        S.Jd = d_Jd ? d_Jd + kb : nullptr;
+        PQP_TRY(plant_launch_step(*p, S, s));
+        const PlantAdvance a{B, p->N, y_floor, S.x, S.U, S.D, d_X + (kb + B_) * p->ns,
+                             (floored && k + 1 < K) ? d_Y : nullptr};
+        PQP_HIP(launch_plant_advance(dyn->data, a, s));
+    }
     return PQP_OK;
 }
 
@@ -2731,6 +2874,7 @@ const KnobRef* find_knob(const char* key) {
         {"iterate_half", &g_tune.iterate_half, nullptr, nullptr},
         {"plant_grid", &pqp::g_plant_grid, nullptr, nullptr},
         {"plant_pipe", &pqp::g_plant_pipe, nullptr, nullptr},
+        {"plant_roll_chain", &pqp::g_plant_roll_chain, nullptr, nullptr},
     };
     for (const KnobRef& k : knobs)
         if (std::strcmp(k.key, key) == 0) return &k;

@@ -46,6 +46,53 @@ int plant_resident_wgs(int N, int M, int nd, int ns, bool pipe);
 // synchronisation.  slots: plant_resident_wgs' count for the form launched.
 hipError_t launch_plant_step(const PlantData& P, const PlantStep& S, int slots, bool pipe, hipStream_t s);
 
+// ---- the closed loop (pqp_plant.hip, pqp.h 2j) ----
+// The state update x+ = (A x + Bu U) + Bd D as the kernels read it: every
+// matrix transposed (k-major), so that the lanes' words of one k are
+// consecutive -- AT [ns][ns], BuT [M][ns], BdT [nd][ns], device buffers.
+struct DynData {
+    int ns, M, nd;
+    const float *AT, *BuT, *BdT;
+};
+// One k_plant_advance launch: xnext [B][ns] from x [B][ns], U [B][M], D [B][nd].
+// Y non-null: the launch also floors Y [B][N] (y_floor > Y_i ? y_floor : Y_i),
+// the rollout chain's step between two control steps.
+struct PlantAdvance {
+    int B, N;
+    float y_floor;
+    const float *x, *U, *D;
+    float *xnext, *Y;
+};
+// What a fused rollout adds to PlantStep, whose arrays then carry a leading K
+// axis (U, h, status, Jp, Jd), whose D is [d_steps][B][nd] and whose x is unused.
+struct PlantRoll {
+    int K, d_steps;  // d_steps: 1 (one D for every step) or K
+    float y_floor;   // > 0: applied before every warm start
+    float* X;        // [K + 1][B][ns]; row 0 read, rows 1..K written
+    DynData dyn;
+};
+// the fused rollout's second kernel argument: the step's, then the rollout's
+struct PlantRollStep : PlantStep {
+    PlantRoll R;
+};
+
+// Tuning key "plant_roll_chain": 1 runs a kind-1 rollout as the chain of
+// step and advance launches too (0, the default: the fused launch).
+extern int g_plant_roll_chain;
+
+// M a k_plant_advance launch takes (above 64, Bu is read from memory, not LDS)
+constexpr int kDynMaxM = 1024;
+// bytes of LDS the dynamics take beside the plant in the fused rollout
+size_t plant_dyn_lds_bytes(int M, int nd, int ns);
+// The fused rollout runs plant_shape_ok's shapes whose dynamics fit the launch's LDS beside the plant.
+bool plant_roll_shape_ok(int N, int M, int nd, int ns);
+// Workgroups of the fused rollout resident on the current device at once; 0 with the error in hipGetLastError.
+int plant_roll_resident_wgs(int N, int M, int nd, int ns);
+// ONE launch each; no allocation, no synchronisation.
+hipError_t launch_plant_roll(const PlantData& P, const PlantStep& S, const PlantRoll& R, int slots, hipStream_t s);
+hipError_t launch_plant_advance(const DynData& d, const PlantAdvance& a, hipStream_t s);
+hipError_t launch_plant_floor(float* Y, size_t n, float y_floor, hipStream_t s);
+
 // ---- the one-workgroup step at horizon sizes (pqp_plant_mid.hip, pqp.h 2g) ----
 // What k_solve_mid2 derives from Qd alone when it stages a problem, found once
 // at create: sym -- Qd bit-symmetric (Y'Qd's column j read as row j); fast -- no

@@ -31,6 +31,14 @@
 //     max_updates by the batched solvers' per-launch budget.
 // Every loop bound is wave-uniform, so the workgroup's barriers (one wave:
 // they only order the LDS traffic) are reached by all 64 lanes.
+//
+// The closed loop (pqp.h 2j) is here too: k_plant_advance, the state update
+// x+ = (A x + Bu U) + Bd D of B states in the reference's matrixMultiply /
+// matrixAdd arithmetic, and k_plant_step's ROLL form, in which the wave takes
+// its state through K steps -- step, outputs, floor, x+, prologue -- with the
+// dynamics staged in LDS behind the plant.
+#include <type_traits>
+
 #include "pqp_device.h"
 #include "pqp_plant.h"
 
@@ -111,10 +119,18 @@ __host__ __device__ constexpr int plant_min_waves(int NMAX, int MMAX, bool PIPE)
     return NMAX <= 24 ? 2 : 1;
 }
 
-template <int NMAX, int MMAX, bool PIPE>
+// ROLL (the fused rollout, pqp.h 2j; S is then a PlantRollStep): a step loop
+// inside the state loop.  The wave carries state b through S.R.K steps: after
+// each it writes the step's outputs, floors Y, forms x+ = (A x + Bu U) + Bd D
+// from the dynamics staged in LDS behind the plant and from the x, U and D it
+// still holds, stores the row of X and runs the prologue on it.  Every ROLL
+// branch is a compile-time one: the step's instantiations (ROLL false, the
+// arguments they always had) compile to the instructions they had without it.
+template <int NMAX, int MMAX, bool PIPE, bool ROLL = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(plant_min_waves(NMAX, MMAX, PIPE))))
-k_plant_step(PlantData P, PlantStep S) {
+k_plant_step(PlantData P, std::conditional_t<ROLL, PlantRollStep, PlantStep> S) {
     static_assert(NMAX % 4 == 0 && MMAX % 4 == 0 && NMAX <= 32 && MMAX <= 32, "one wave");
+    static_assert(!(ROLL && PIPE), "the rollout has the plain iteration only");
     if ((int)blockIdx.x >= S.B) return;  // a wave without a state
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int N = P.N, M = P.M, nd = P.nd, ns = P.ns;
@@ -147,6 +163,12 @@ k_plant_step(PlantData P, PlantStep S) {
     for (int e = lane; e < nd; e += 64) lds[L.Mp5 + e] = P.Mp5[e];
     for (int e = lane; e < N * M; e += 64) lds[L.GQ + (e / M) * L.lg + e % M] = P.GQ[e];
     for (int e = lane; e < M * M; e += 64) lds[L.Qi + e] = P.Qinv[e];
+    if constexpr (ROLL) {  // the dynamics, k-major as they are stored, behind the plant
+        float* const dl = lds + L.total;
+        for (int e = lane; e < ns * ns; e += 64) dl[e] = S.R.dyn.AT[e];
+        for (int e = lane; e < M * ns; e += 64) dl[ns * ns + e] = S.R.dyn.BuT[e];
+        for (int e = lane; e < nd * ns; e += 64) dl[ns * ns + M * ns + e] = S.R.dyn.BdT[e];
+    }
     const float Mp6 = P.Mp6[0];
 
     // ---- once per wave: the solve loop's matrices (k_solve_wave's setup, with
@@ -222,7 +244,12 @@ k_plant_step(PlantData P, PlantStep S) {
         }
     };
 
+    int steps = 1;
+    if constexpr (ROLL) steps = S.R.K;
+    float ycarry = 0.0f;  // ROLL: the previous step's Y, lanes < N
     for (long long b = blockIdx.x; b < S.B; b += gridDim.x) {
+        int k = 0;
+        do {  // ROLL: state b's K steps; else once (the body keeps the state loop's indentation)
         // ---- the state's prologue.  Its lane numbers, sizes and LDS offsets
         // are derived afresh from opaque copies, so that none of them is
         // hoisted out of the state loop and held in a register through the
@@ -242,11 +269,23 @@ k_plant_step(PlantData P, PlantStep S) {
         const float* const Qis = lds + Q.Qi;
         const int pm = ln < Mq ? ln : 0, pn = ln < Np ? ln : 0, pns = ln < nsp ? ln : 0, pnd = ln < ndp ? ln : 0;
         // x, D, the bounds, and the solve loop's vectors as a fresh workgroup has them
-        if (ln < nsp) xs[ln] = S.x[(size_t)b * nsp + ln];
-        if (ln < ndp) ds[ln] = S.D[(size_t)b * ndp + ln];
-        const float kp = S.Kp ? ((lane < N) ? S.Kp[(size_t)b * N + lane] : 0.0f) : kp_plant;
+        if constexpr (ROLL) {  // x: row 0 of X, then the x+ the previous step left in xs; D: this step's
+            if (k == 0 && ln < nsp) xs[ln] = S.R.X[(size_t)b * nsp + ln];
+            const float* const Dk = S.D + (S.R.d_steps > 1 ? (size_t)k * S.B * ndp : (size_t)0);
+            if (ln < ndp) ds[ln] = Dk[(size_t)b * ndp + ln];
+        } else {
+            if (ln < nsp) xs[ln] = S.x[(size_t)b * nsp + ln];
+            if (ln < ndp) ds[ln] = S.D[(size_t)b * ndp + ln];
+        }
+        const float kp = S.Kp ? ((lane < N) ? S.Kp[(size_t)b * N + (ROLL ? ln : lane)] : 0.0f) : kp_plant;
         if (ln < 32) {
-            ya[ln] = (ln < Np) ? (S.warm ? S.Y[(size_t)b * Np + ln] : 1000.0f) : 0.0f;  // initMat(Y, 1000) :710
+            if constexpr (ROLL) {  // warm from the previous step's Y (k > 0); floored before every warm start
+                float y0 = (k > 0) ? ycarry : ((ln < Np) ? (S.warm ? S.Y[(size_t)b * Np + ln] : 1000.0f) : 0.0f);
+                if ((k > 0 || S.warm) && S.R.y_floor > 0.0f && ln < Np) y0 = S.R.y_floor > y0 ? S.R.y_floor : y0;
+                ya[ln] = y0;
+            } else {
+                ya[ln] = (ln < Np) ? (S.warm ? S.Y[(size_t)b * Np + ln] : 1000.0f) : 0.0f;  // initMat(Y, 1000) :710
+            }
             yb[ln] = 0.0f;
             rowb[ln] = 0.0f;
             tb[ln] = ub[ln] = rpb[ln] = 0.0f;
@@ -453,15 +492,131 @@ k_plant_step(PlantData P, PlantStep S) {
         }
         // ---- the state's results ----
         const float* yfin = cb ? yb : ya;
-        if (lane < N) S.Y[(size_t)b * N + lane] = yfin[lane];
-        if (lane < M) S.U[(size_t)b * M + lane] = u_last;  // computeUfromY wrote U on every terminate(): the last one stands
-        if (lane == 0) {
-            if (S.h) S.h[b] = h;
-            if (S.status) S.status[b] = status;
-            if (S.Jp) S.Jp[b] = have ? Jp_last : __builtin_nanf("");
-            if (S.Jd) S.Jd[b] = have ? Jd_last : __builtin_nanf("");
+        if constexpr (ROLL) {
+            // ---- the step's results, row k of the [K][B] arrays; Y is the last step's.  Lane
+            // numbers, sizes and offsets from opaque copies, as the prologue's ----
+            int l2 = lane, N2 = N, M2 = M, nd2 = nd, ns2 = ns;
+            asm volatile("" : "+v"(l2), "+s"(N2), "+s"(M2), "+s"(nd2), "+s"(ns2));
+            const size_t kb = (size_t)k * S.B + b;
+            if (k == steps - 1 && l2 < N2) S.Y[(size_t)b * N2 + l2] = yfin[l2];
+            if (l2 < M2) S.U[kb * M2 + l2] = u_last;
+            if (l2 == 0) {
+                if (S.h) S.h[kb] = h;
+                if (S.status) S.status[kb] = status;
+                if (S.Jp) S.Jp[kb] = have ? Jp_last : __builtin_nanf("");
+                if (S.Jd) S.Jd[kb] = have ? Jd_last : __builtin_nanf("");
+            }
+            // ---- x+ = (A x + 1 Bu U) + 1 Bd D, one lane per row: three matrixMultiply (:84), two
+            // matrixAdd (:157), from the x, U (the last terminate()'s, in ub) and D in LDS.  Not
+            // unrolled: a few hundred products per step, beside the solve loop's live registers ----
+            const float* const ATs = lds + plant_lds(N2, M2, nd2, ns2).total;
+            const float* const BuTs = ATs + ns2 * ns2;
+            const float* const BdTs = BuTs + M2 * ns2;
+            const int pr = l2 < ns2 ? l2 : 0;
+            float t = 0.0f, v = 0.0f, w = 0.0f;
+#pragma unroll 1
+            for (int j = 0; j < ns2; ++j) t += ATs[j * ns2 + pr] * xs[j];
+#pragma unroll 1
+            for (int j = 0; j < M2; ++j) v += BuTs[j * ns2 + pr] * ub[j];
+#pragma unroll 1
+            for (int j = 0; j < nd2; ++j) w += BdTs[j * ns2 + pr] * ds[j];
+            float xn = t + 1.0f * v;
+            xn = xn + 1.0f * w;
+            const float yc = (l2 < N2) ? yfin[l2] : 0.0f;
+            __syncthreads();  // x, U, D and Y are read: xs and, in the next prologue, the rest are rewritten
+            ycarry = yc;
+            if (l2 < ns2) {
+                xs[l2] = xn;
+                S.R.X[((size_t)(k + 1) * S.B + b) * ns2 + l2] = xn;
+            }
+        } else {
+            if (lane < N) S.Y[(size_t)b * N + lane] = yfin[lane];
+            if (lane < M) S.U[(size_t)b * M + lane] = u_last;  // computeUfromY wrote U on every terminate(): the last one stands
+            if (lane == 0) {
+                if (S.h) S.h[b] = h;
+                if (S.status) S.status[b] = status;
+                if (S.Jp) S.Jp[b] = have ? Jp_last : __builtin_nanf("");
+                if (S.Jd) S.Jd[b] = have ? Jd_last : __builtin_nanf("");
+            }
         }
         __syncthreads();  // the next state's stores come after this one's reads
+        } while (ROLL && ++k < steps);
+    }
+}
+
+// ---- x+ = (A x + 1 Bu U) + 1 Bd D for B states (pqp_dynamics_advance, the
+// rollout chain): one lane per row of x+, one wave per state at a time, four
+// waves per workgroup; AT, BdT and (M <= 64) BuT staged in LDS once per
+// workgroup, k-major, so a wave's words of one k are consecutive.  A wider Bu
+// (the shared plant's M) is read from memory, k-major too.  Sums as the
+// reference's matrixMultiply (:84): k in order from +0.0f, every product
+// rounded before its add; then matrixAdd (:157) twice.  The group loop's bound
+// is workgroup-uniform, so every wave reaches the barriers. ----
+constexpr int kAdvWaves = 4;
+
+__host__ __device__ inline int advance_lds_floats(int ns, int M, int nd) {
+    return ns * ns + (M <= 64 ? M * ns : 0) + nd * ns + kAdvWaves * 192;
+}
+
+__global__ void __launch_bounds__(64 * kAdvWaves) k_plant_advance(DynData d, PlantAdvance a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int ns = d.ns, M = d.M, nd = d.nd;
+    const bool bu_lds = M <= 64;
+    float* const ATs = lds;
+    float* const BuTs = ATs + ns * ns;
+    float* const BdTs = BuTs + (bu_lds ? M * ns : 0);
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    float* const xv = BdTs + nd * ns + wave * 192;  // this wave's x, D, U: 64 words each
+    float* const dv = xv + 64;
+    float* const uv = xv + 128;
+    for (int e = tid; e < ns * ns; e += 64 * kAdvWaves) ATs[e] = d.AT[e];
+    if (bu_lds)
+        for (int e = tid; e < M * ns; e += 64 * kAdvWaves) BuTs[e] = d.BuT[e];
+    for (int e = tid; e < nd * ns; e += 64 * kAdvWaves) BdTs[e] = d.BdT[e];
+    __syncthreads();
+    const int pr = lane < ns ? lane : 0;
+    const long long groups = ((long long)a.B + kAdvWaves - 1) / kAdvWaves;
+    for (long long g = blockIdx.x; g < groups; g += gridDim.x) {
+        const long long b = g * kAdvWaves + wave;
+        const bool live = b < a.B;  // wave-uniform
+        if (live) {
+            if (lane < ns) xv[lane] = a.x[(size_t)b * ns + lane];
+            if (lane < nd) dv[lane] = a.D[(size_t)b * nd + lane];
+            if (bu_lds && lane < M) uv[lane] = a.U[(size_t)b * M + lane];
+        }
+        __syncthreads();
+        if (live) {
+            float t = 0.0f, v = 0.0f, w = 0.0f;
+#pragma unroll 4
+            for (int j = 0; j < ns; ++j) t += ATs[j * ns + pr] * xv[j];
+            if (bu_lds) {
+#pragma unroll 4
+                for (int j = 0; j < M; ++j) v += BuTs[j * ns + pr] * uv[j];
+            } else {
+                const float* const Ub = a.U + (size_t)b * M;
+#pragma unroll 4
+                for (int j = 0; j < M; ++j) v += d.BuT[(size_t)j * ns + pr] * Ub[j];
+            }
+#pragma unroll 4
+            for (int j = 0; j < nd; ++j) w += BdTs[j * ns + pr] * dv[j];
+            float xn = t + 1.0f * v;
+            xn = xn + 1.0f * w;
+            if (lane < ns) a.xnext[(size_t)b * ns + lane] = xn;
+            if (a.Y)
+                for (int i = lane; i < a.N; i += 64) {
+                    const float y = a.Y[(size_t)b * a.N + i];
+                    a.Y[(size_t)b * a.N + i] = a.y_floor > y ? a.y_floor : y;
+                }
+        }
+        __syncthreads();  // the next group's x, D, U come after this one's reads
+    }
+}
+
+// Y_i = y_floor > Y_i ? y_floor : Y_i over n words: the floor before a rollout chain's first, warm, step
+__global__ void __launch_bounds__(256) k_plant_floor(float* Y, size_t n, float y_floor) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const float y = Y[i];
+        Y[i] = y_floor > y ? y_floor : y;
     }
 }
 
@@ -486,7 +641,70 @@ PlantKernel plant_kernel(int N, int M, bool pipe) {
     return pipe ? plant_kernel_n<true>(N, M) : plant_kernel_n<false>(N, M);
 }
 
+typedef void (*RollKernel)(PlantData, PlantRollStep);
+
+template <int NMAX>
+RollKernel roll_kernel_m(int M) {
+    if (M <= 8) return k_plant_step<NMAX, 8, false, true>;
+    if (M <= 16) return k_plant_step<NMAX, 16, false, true>;
+    return k_plant_step<NMAX, 32, false, true>;
+}
+RollKernel roll_kernel(int N, int M) {  // plant_kernel's widths
+    if (N <= 8) return roll_kernel_m<8>(M);
+    if (N <= 16) return roll_kernel_m<16>(M);
+    if (N <= 24) return roll_kernel_m<24>(M);
+    if (N <= 28) return roll_kernel_m<28>(M);
+    return roll_kernel_m<32>(M);
+}
+
 }  // namespace
+
+int g_plant_roll_chain = 0;
+
+size_t plant_dyn_lds_bytes(int M, int nd, int ns) { return sizeof(float) * ((size_t)ns * ns + (size_t)M * ns + (size_t)nd * ns); }
+
+bool plant_roll_shape_ok(int N, int M, int nd, int ns) {
+    return plant_shape_ok(N, M, nd, ns) && plant_lds_bytes(N, M, nd, ns) + plant_dyn_lds_bytes(M, nd, ns) <= kPlantLdsBudget;
+}
+
+int plant_roll_resident_wgs(int N, int M, int nd, int ns) {
+    int dev = 0, cus = 0, per_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, roll_kernel(N, M), 64,
+                                                     plant_lds_bytes(N, M, nd, ns) + plant_dyn_lds_bytes(M, nd, ns)) !=
+        hipSuccess)
+        return 0;
+    return cus * per_cu;
+}
+
+hipError_t launch_plant_roll(const PlantData& P, const PlantStep& S, const PlantRoll& R, int slots, hipStream_t s) {
+    int grid = S.B < slots ? S.B : slots;
+    if (g_plant_grid > 0 && grid > g_plant_grid) grid = g_plant_grid;
+    if (grid < 1) grid = 1;
+    PlantRollStep SR{};
+    static_cast<PlantStep&>(SR) = S;
+    SR.R = R;
+    hipLaunchKernelGGL(roll_kernel(P.N, P.M), dim3(grid), dim3(64),
+                       plant_lds_bytes(P.N, P.M, P.nd, P.ns) + plant_dyn_lds_bytes(P.M, P.nd, P.ns), s, P, SR);
+    return hipGetLastError();
+}
+
+hipError_t launch_plant_advance(const DynData& d, const PlantAdvance& a, hipStream_t s) {
+    const long long groups = ((long long)a.B + kAdvWaves - 1) / kAdvWaves;
+    int grid = (int)(groups < 2048 ? groups : 2048);
+    if (g_plant_grid > 0 && grid > g_plant_grid) grid = g_plant_grid;
+    if (grid < 1) grid = 1;
+    hipLaunchKernelGGL(k_plant_advance, dim3(grid), dim3(64 * kAdvWaves),
+                       sizeof(float) * (size_t)advance_lds_floats(d.ns, d.M, d.nd), s, d, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_plant_floor(float* Y, size_t n, float y_floor, hipStream_t s) {
+    const size_t blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(k_plant_floor, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, s, Y, n, y_floor);
+    return hipGetLastError();
+}
 
 size_t plant_lds_bytes(int N, int M, int nd, int ns) { return sizeof(float) * (size_t)plant_lds(N, M, nd, ns).total; }
 

@@ -123,6 +123,12 @@ SIGNATURES = {
     "pqp_shared_create_plant": (C.c_int, [C.c_int] * 5 + [_fp] * 12 + [C.POINTER(C.c_void_p)]),
     "pqp_shared_max_updates": (C.c_longlong, [_vp]),
     "pqp_shared_step": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_longlong] + [_vp] * 10 + [_vp]),
+    "pqp_dynamics_create": (C.c_int, [C.c_int] * 4 + [_fp] * 3 + [C.POINTER(C.c_void_p)]),
+    "pqp_dynamics_destroy": (C.c_int, [_vp]),
+    "pqp_dynamics_advance": (C.c_int, [_vp, C.c_int] + [_vp] * 4 + [_vp]),
+    "pqp_plant_rollout_fused": (C.c_int, [C.c_int] * 4),
+    "pqp_plant_rollout": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.c_float,
+                                    C.c_longlong] + [_vp] * 6 + [_vp]),
     "pqp_rowblock_create": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, C.POINTER(C.c_void_p)]),
     "pqp_rowblock_update": (C.c_int, [_vp, _vp, _vp, _vp]),
     "pqp_rowblock_check": (C.c_int, [_vp, _vp]),
@@ -964,6 +970,7 @@ class Plant:
         self.N, self.M, self.nd, self.ns = int(N), int(M), int(nd), int(ns)
         self._h = None
         self.B = 0
+        self._roll_K = 0  # K of the rollout whose outputs the tensors hold; 0: a step's
         sizes = dict(Qp_inv=M * M, Gp=N * M, Kp=N, Fp1=M * nd, Fp2=M * ns, Fp3=M, Mp1=ns * ns, Mp2=nd * ns,
                      Mp3=nd * nd, Mp4=ns, Mp5=nd, Mp6=1)
         host = {}
@@ -1032,11 +1039,12 @@ class Plant:
         torch = self.torch
         f = dict(dtype=torch.float32, device=self.device)
         B = int(x.shape[0]) if hasattr(x, "shape") and len(x.shape) == 2 else len(x)
-        if B != self.B:
+        if B != self.B or self._roll_K:  # (after a rollout the outputs carry its K axis: made anew, Y kept)
             if B <= 0:
                 _check(lib().pqp_plant_step(self._h, B, *([None] * 3), 0, 1, *([None] * 10), None))
-            self.B = B
-            self.Y, self.U = torch.zeros(B, self.N, **f), torch.zeros(B, self.M, **f)
+            Y = self.Y if B == self.B else torch.zeros(B, self.N, **f)
+            self.B, self._roll_K = B, 0
+            self.Y, self.U = Y, torch.zeros(B, self.M, **f)
             self.h = torch.zeros(B, dtype=torch.int64, device=self.device)
             self.status = torch.zeros(B, dtype=torch.int32, device=self.device)
             self.Fp, self.Fd = torch.zeros(B, self.M, **f), torch.zeros(B, self.N, **f)
@@ -1063,9 +1071,128 @@ class Plant:
                                     *[p(getattr(self, k)) for k in self.OUT], stream))
         return self
 
+    @staticmethod
+    def rollout_fused(N: int, M: int, nd: int, ns: int) -> bool:
+        """True where ``rollout`` of that shape is one launch (pqp_plant_rollout_fused)."""
+        return bool(lib().pqp_plant_rollout_fused(int(N), int(M), int(nd), int(ns)))
+
+    def rollout(self, x0, K: int, dynamics: "Dynamics", D=None, Kp=None, warm: bool = False,
+                floor: float | None = None, max_updates: int | None = None):
+        """K control steps of the states ``x0`` [B, ns] under ``dynamics``
+        (pqp_plant_rollout, section 2j): step, x+ = (A x + Bu U) + Bd D, warm
+        step, ... without leaving the device -- one launch for the one-wave
+        plants, a chain of launches for ``horizon=True`` ones.  Fills the
+        device tensors X [K+1, B, ns] (row 0 is x0), U [K, B, M], h, status,
+        Jp, Jd [K, B] and Y [B, N] (step K-1's) and returns self; step k of
+        state b holds what ``step`` gives at X[k, b].  Runs on torch's current
+        stream and does not synchronise.
+
+        D [B, nd] (every step's) or [K, B, nd]; None: the plant's own D.
+        Kp [B, N] or None, constant over the steps.  warm: step 0 starts from
+        the rows of ``self.Y``; later steps always start from the previous
+        step's Y.  floor: Y is floored before every warm start (unlike
+        ``step``'s, it does not make step 0 warm).  max_updates: per step."""
+        torch = self.torch
+        f = dict(dtype=torch.float32, device=self.device)
+        K = int(K)
+        B = int(x0.shape[0]) if hasattr(x0, "shape") and len(x0.shape) == 2 else len(x0)
+        if B <= 0 or K <= 0:
+            _check(lib().pqp_plant_rollout(self._h, dynamics._h, B, K, None, None, 1, None, 0, 0.0, 1, *([None] * 6), None))
+        if B != self.B or self._roll_K != K:
+            keep_Y = B == self.B
+            self.B, self._roll_K = B, K
+            if not keep_Y:
+                self.Y = torch.zeros(B, self.N, **f)
+            self.X, self.U = torch.zeros(K + 1, B, self.ns, **f), torch.zeros(K, B, self.M, **f)
+            self.h = torch.zeros(K, B, dtype=torch.int64, device=self.device)
+            self.status = torch.zeros(K, B, dtype=torch.int32, device=self.device)
+            self.Jp, self.Jd = torch.zeros(K, B, **f), torch.zeros(K, B, **f)
+            self._Dt = None
+        self.X[0].copy_(self._dev(x0, self.ns, "x0"))
+        if D is None:
+            if self._D is None:
+                raise ValueError("Plant.rollout: this plant has no default D")
+            if self._Dt is None:
+                self._Dt = torch.as_tensor(np.tile(self._D, (B, 1)), **f).contiguous()
+            Dt, d_steps = self._Dt, 1
+        else:
+            if not torch.is_tensor(D):
+                D = np.ascontiguousarray(np.asarray(D, np.float32))
+            Dt = torch.as_tensor(D, **f).contiguous()
+            d_steps = K if Dt.dim() == 3 else 1
+            if tuple(Dt.shape) not in ((B, self.nd), (K, B, self.nd)):
+                raise ValueError(f"Plant.rollout: D must be [{B}, {self.nd}] or [{K}, {B}, {self.nd}]")
+        Kt = None if Kp is None else self._dev(Kp, self.N, "Kp")
+        p = ProblemBatch._p
+        cap = self.max_updates if max_updates is None else int(max_updates)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._inputs = (Dt, Kt, dynamics)  # alive until the next call: the launches are asynchronous
+        _check(lib().pqp_plant_rollout(self._h, dynamics._h, B, K, p(self.X), p(Dt), d_steps, None if Kt is None else p(Kt),
+                                       int(bool(warm)), 0.0 if floor is None else float(floor), cap, p(self.Y), p(self.U),
+                                       p(self.h), p(self.status), p(self.Jp), p(self.Jd), stream))
+        return self
+
     def close(self):
         if self._h is not None:
             lib().pqp_plant_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Dynamics:
+    """A plant's state update x+ = (A x + Bu U) + Bd D resident on the device
+    (pqp_dynamics_* of include/pqp.h, section 2j), in the reference's
+    matrixMultiply / matrixAdd arithmetic.  A [ns, ns], Bu [ns, M], Bd [ns, nd],
+    row-major; 1 <= ns, nd <= 64.  ``Plant.rollout`` takes one; ``advance``
+    is the single step."""
+
+    def __init__(self, ns: int, M: int, nd: int, A, Bu, Bd, device=None):
+        self.ns, self.M, self.nd = int(ns), int(M), int(nd)
+        self._h = None
+        host = dict(A=_f32(A).reshape(-1), Bu=_f32(Bu).reshape(-1), Bd=_f32(Bd).reshape(-1))
+        sizes = dict(A=self.ns * self.ns, Bu=self.ns * self.M, Bd=self.ns * self.nd)
+        import torch
+
+        for k, a in host.items():
+            if a.size != sizes[k]:
+                raise ValueError(f"Dynamics: {k} has {a.size} values, not {sizes[k]}")
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        dev = self.device.index if self.device.index is not None else -1
+        h = C.c_void_p()
+        _check(lib().pqp_dynamics_create(dev, self.ns, self.M, self.nd, _buf(host["A"]), _buf(host["Bu"]), _buf(host["Bd"]),
+                                         C.byref(h)))
+        self._h = h
+
+    def advance(self, x, U, D, out=None):
+        """x+ [B, ns] of the device tensors x [B, ns], U [B, M], D [B, nd] (contiguous float32, on this
+        device): one launch on torch's current stream, no synchronisation.  ``out`` must not overlap x."""
+        import torch
+
+        B = int(x.shape[0])
+        if out is None:
+            out = torch.empty_like(x)
+        for t, cols, what in ((x, self.ns, "x"), (U, self.M, "U"), (D, self.nd, "D"), (out, self.ns, "out")):
+            if not (torch.is_tensor(t) and t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (B, cols)):
+                raise ValueError(f"Dynamics.advance: {what} must be a contiguous float32 tensor [{B}, {cols}]")
+        p = ProblemBatch._p
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _check(lib().pqp_dynamics_advance(self._h, B, p(x), p(U), p(D), p(out), stream))
+        return out
+
+    def close(self):
+        if self._h is not None:
+            lib().pqp_dynamics_destroy(self._h)
             self._h = None
 
     def __enter__(self):
