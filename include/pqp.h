@@ -502,7 +502,8 @@ int pqp_batch_solve_from(int B, int N, int M, const float *d_Qd, const float *d_
  * buffers, so steps on different streams may run concurrently without a lock;
  * it runs on the plant's device whatever device the caller has current (and
  * restores the caller's), and does no allocation, no synchronisation and no
- * copy to the host.
+ * copy to the host.  The stopping rule is the reference's; pqp_plant_step_tol
+ * (2k) adds a caller-set tolerance on the gap.
  * -------------------------------------------------------------------- */
 typedef struct pqp_plant pqp_plant;
 
@@ -568,7 +569,8 @@ int pqp_plant_step(pqp_plant *p, int B, const float *d_x, const float *d_D, cons
  * nd <= 64, ns <= 64, N <= 192, and (N, M) one that the batched path 3
  * (pqp_batch_solve_path(N, M) == 3 at default tuning) solves within one
  * workgroup's LDS with the plant step's own words added -- 140 x 35 and
- * 40 x 12 among them.  Converge mode only.
+ * 40 x 12 among them.  Converge mode only.  pqp_plant_step_tol (2k) runs on
+ * either kind of handle too.
  * -------------------------------------------------------------------- */
 
 /* 0: (N, M, nd, ns) is no shape pqp_plant_step runs; 1: the one-wave step of 2f
@@ -614,7 +616,8 @@ int pqp_plant_create_horizon(int device, int N, int M, int nd, int ns, const flo
  * there whatever device the caller has current, and restore the caller's.
  * Calls on different streams may run concurrently: a solve's per-state resume
  * words are allocated per call.  Argument errors (a null handle or pointer,
- * B <= 0) are PQP_ERR_ARG before any device is looked for.
+ * B <= 0) are PQP_ERR_ARG before any device is looked for.  A gap tolerance
+ * beside the reference's stopping rule: pqp_shared_solve_tol (2k).
  * -------------------------------------------------------------------- */
 typedef struct pqp_shared pqp_shared;
 
@@ -680,7 +683,8 @@ int pqp_shared_solve(pqp_shared *p, int B, const float *d_Fd, const float *d_Md,
  * pqp_shared_destroy work on either kind of handle, with the same results.
  * Argument errors (a null handle or required pointer, B <= 0, a cap out of
  * range, a handle without plant matrices) are PQP_ERR_ARG before any device is
- * looked for.
+ * looked for.  A gap tolerance beside the reference's stopping rule:
+ * pqp_shared_step_tol (2k).
  * -------------------------------------------------------------------- */
 
 /* States per workgroup the step uses for (N, M, nd, ns): pqp_shared_states(N, M) where the
@@ -743,7 +747,9 @@ int pqp_shared_step(pqp_shared *p, int B, const float *d_x, const float *d_D, co
  * asynchronous on `stream`, no allocation, no synchronisation, no copy to the
  * host, the caller's device restored, so it can be captured in a graph; it
  * works on both kinds of pqp_plant.  Every argument error is PQP_ERR_ARG
- * before any device is looked for.
+ * before any device is looked for.  Steps with active bounds often settle one
+ * ulp above the reference's exact-float stop and run to the cap:
+ * pqp_plant_rollout_tol (2k) takes a tolerance on the gap.
  * -------------------------------------------------------------------- */
 typedef struct pqp_dynamics pqp_dynamics;
 
@@ -779,6 +785,64 @@ int pqp_plant_rollout(pqp_plant *p, const pqp_dynamics *dyn, int B, int K, float
                       int D_steps, const float *d_Kp, int warm, float y_floor, long long max_updates,
                       float *d_Y, float *d_U, long long *d_h, int *d_status, float *d_Jp, float *d_Jd,
                       void *stream);
+
+/* ----------------------------------------------------------------------
+ * 2k. A gap tolerance for the plant family's stopping rule (2f to 2j).
+ * terminate() (PQP_CPU.c:673-687) stops when the float32 gap Jp + Jd is <= 0:
+ * its tolerances eaj = erj = 1e-6 never decide at the plants' costs (|Jd| about
+ * 1.5e5, where one float32 ulp is 0.0156), so a gap that settles one ulp above
+ * zero runs to the cap.  The four _tol entry points below take a caller-set
+ * tolerance on that gap; the reference's rule stays the default and stays bit
+ * for bit (the entry points of 2f to 2j ARE these with abs_tol = rel_tol = 0).
+ *
+ * The rule, for an iterate that passed checkFeas (nothing else is evaluated
+ * for any other), in this order:
+ *   1. the reference's own tests (:682-685) pass: stop, status PQP_STATUS_DONE;
+ *   2. both tolerances 0: go on;
+ *   3. gap = (double)(Jp + Jd), the float32 sum as :683;
+ *      gap <= abs_tol, or gap <= (double)rel_tol * fabs((double)Jd): stop,
+ *      status PQP_STATUS_TOL;
+ *   4. go on.
+ * The reference's test is tried first, so a tolerance can only stop a solve
+ * earlier, never later; a NaN gap or a NaN Jd matches no tolerance.  Y, U, h,
+ * Jp and Jd of a state are those of the iterate it stopped at, as before: the
+ * iterates themselves do not depend on the tolerances.  PQP_STATUS_TOL appears
+ * only when a tolerance is positive.
+ *
+ * A tolerance that is negative, NaN or infinite is PQP_ERR_ARG before any
+ * device is looked for (and before any other argument is looked at).  The
+ * single-problem handles, pqp_batch_solve* and the drop-ins keep the
+ * reference's rule.
+ * -------------------------------------------------------------------- */
+#define PQP_STATUS_DONE 1   /* the reference's terminate() returned 1                         */
+#define PQP_STATUS_CAPPED 2 /* max_updates reached                                             */
+#define PQP_STATUS_TOL 3    /* within abs_tol / rel_tol where the reference's test had not passed */
+
+/* The rule above on the host, the same inline function the kernels call: 0 go on, 1 the
+ * reference's tests pass, 3 within the tolerances.  No device needed, no error set, no
+ * validation: the tolerances are taken as given (a negative or NaN one never matches). */
+int pqp_stop_decide(float Jp, float Jd, float abs_tol, float rel_tol);
+
+/* pqp_plant_step (2f, 2g), pqp_plant_rollout (2j), pqp_shared_solve (2h) and pqp_shared_step (2i)
+ * with the two tolerances before `stream`.  Every other word of those contracts holds: the
+ * launches, asynchrony, no allocation (pqp_shared_solve_tol: as pqp_shared_solve), graph
+ * capture, both kinds of pqp_plant, the fused rollout and the chain, which give the same bits. */
+int pqp_plant_step_tol(pqp_plant *p, int B, const float *d_x, const float *d_D, const float *d_Kp, int warm,
+                       long long max_updates, float *d_Y, float *d_U, long long *d_h, int *d_status,
+                       float *d_Fp, float *d_Mp, float *d_Fd, float *d_Md, float *d_Jp, float *d_Jd,
+                       float abs_tol, float rel_tol, void *stream);
+int pqp_plant_rollout_tol(pqp_plant *p, const pqp_dynamics *dyn, int B, int K, float *d_X, const float *d_D,
+                          int D_steps, const float *d_Kp, int warm, float y_floor, long long max_updates,
+                          float *d_Y, float *d_U, long long *d_h, int *d_status, float *d_Jp, float *d_Jd,
+                          float abs_tol, float rel_tol, void *stream);
+int pqp_shared_solve_tol(pqp_shared *p, int B, const float *d_Fd, const float *d_Md, const float *d_Fp,
+                         const float *d_Mp, const float *d_Kp, long long max_updates, const float *d_Y0,
+                         float *d_Y, float *d_U, long long *d_h, int *d_status, float *d_Jp, float *d_Jd,
+                         float abs_tol, float rel_tol, void *stream);
+int pqp_shared_step_tol(pqp_shared *p, int B, const float *d_x, const float *d_D, const float *d_Kp, int warm,
+                        long long max_updates, float *d_Y, float *d_U, long long *d_h, int *d_status,
+                        float *d_Fp, float *d_Mp, float *d_Fd, float *d_Md, float *d_Jp, float *d_Jd,
+                        float abs_tol, float rel_tol, void *stream);
 
 #ifdef __cplusplus
 }

@@ -18,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "pqp_device.h"  // stop_decide: pqp_stop_decide is the kernels' own inline function, on the host
 #include "pqp_internal.h"
 #include "pqp_launch.h"
 #include "pqp_plant.h"
@@ -1166,7 +1167,7 @@ using namespace pqp;
 
 extern "C" {
 
-int pqp_version(void) { return 113; }  // ABI revision: INTEGRATION.md section 6
+int pqp_version(void) { return 114; }  // ABI revision: INTEGRATION.md section 6
 
 // ---------------------------------------------------------------------------
 // 2a. status-returning host API
@@ -2181,16 +2182,28 @@ static int plant_launch_step(const pqp_plant& p, const PlantStep& S, hipStream_t
     return PQP_OK;
 }
 
-int pqp_plant_step(pqp_plant* p, int B, const float* d_x, const float* d_D, const float* d_Kp, int warm,
-                   long long max_updates, float* d_Y, float* d_U, long long* d_h, int* d_status, float* d_Fp,
-                   float* d_Mp, float* d_Fd, float* d_Md, float* d_Jp, float* d_Jd, void* stream) {
-    if (!p) return set_error(PQP_ERR_ARG, "pqp_plant_step: null plant");
-    if (B <= 0) return set_error(PQP_ERR_ARG, "pqp_plant_step: B = %d states", B);
-    if (!d_x || !d_D || !d_Y || !d_U) return set_error(PQP_ERR_ARG, "pqp_plant_step: null d_x, d_D, d_Y or d_U");
+// 2k: a tolerance is a finite float >= 0 (-0.0f counts as 0); checked before anything else of a _tol call
+static int check_tols(const char* fn, float abs_tol, float rel_tol) {
+    if (!(abs_tol >= 0.0f) || std::isinf(abs_tol))
+        return set_error(PQP_ERR_ARG, "%s: abs_tol = %g is not a finite value >= 0", fn, (double)abs_tol);
+    if (!(rel_tol >= 0.0f) || std::isinf(rel_tol))
+        return set_error(PQP_ERR_ARG, "%s: rel_tol = %g is not a finite value >= 0", fn, (double)rel_tol);
+    return PQP_OK;
+}
+
+// pqp_plant_step (fn names the caller in messages; tolerances 0, 0) and pqp_plant_step_tol
+static int plant_step(const char* fn, pqp_plant* p, int B, const float* d_x, const float* d_D, const float* d_Kp,
+                      int warm, long long max_updates, float* d_Y, float* d_U, long long* d_h, int* d_status,
+                      float* d_Fp, float* d_Mp, float* d_Fd, float* d_Md, float* d_Jp, float* d_Jd, float abs_tol,
+                      float rel_tol, void* stream) {
+    PQP_TRY(check_tols(fn, abs_tol, rel_tol));
+    if (!p) return set_error(PQP_ERR_ARG, "%s: null plant", fn);
+    if (B <= 0) return set_error(PQP_ERR_ARG, "%s: B = %d states", fn, B);
+    if (!d_x || !d_D || !d_Y || !d_U) return set_error(PQP_ERR_ARG, "%s: null d_x, d_D, d_Y or d_U", fn);
     const long long cap = pqp::batch_chunk_for(p->N, p->M);
     if (max_updates < 1 || max_updates > cap)
-        return set_error(PQP_ERR_ARG, "pqp_plant_step: max_updates = %lld is outside 1 .. %lld (pqp_plant_max_updates: "
-                                      "one launch's budget)", max_updates, cap);
+        return set_error(PQP_ERR_ARG, "%s: max_updates = %lld is outside 1 .. %lld (pqp_plant_max_updates: "
+                                      "one launch's budget)", fn, max_updates, cap);
     PlantStep S{};
     S.B = B;
     S.warm = warm ? 1 : 0;
@@ -2198,8 +2211,24 @@ int pqp_plant_step(pqp_plant* p, int B, const float* d_x, const float* d_D, cons
     S.x = d_x, S.D = d_D, S.Kp = d_Kp;
     S.Y = d_Y, S.U = d_U, S.h = d_h, S.status = d_status;
     S.Fp = d_Fp, S.Mp = d_Mp, S.Fd = d_Fd, S.Md = d_Md, S.Jp = d_Jp, S.Jd = d_Jd;
+    S.abs_tol = abs_tol, S.rel_tol = rel_tol;
     DeviceGuard on(p->dev);
     return plant_launch_step(*p, S, static_cast<hipStream_t>(stream));
+}
+
+int pqp_plant_step(pqp_plant* p, int B, const float* d_x, const float* d_D, const float* d_Kp, int warm,
+                   long long max_updates, float* d_Y, float* d_U, long long* d_h, int* d_status, float* d_Fp,
+                   float* d_Mp, float* d_Fd, float* d_Md, float* d_Jp, float* d_Jd, void* stream) {
+    return plant_step("pqp_plant_step", p, B, d_x, d_D, d_Kp, warm, max_updates, d_Y, d_U, d_h, d_status, d_Fp, d_Mp,
+                      d_Fd, d_Md, d_Jp, d_Jd, 0.0f, 0.0f, stream);
+}
+
+int pqp_plant_step_tol(pqp_plant* p, int B, const float* d_x, const float* d_D, const float* d_Kp, int warm,
+                       long long max_updates, float* d_Y, float* d_U, long long* d_h, int* d_status, float* d_Fp,
+                       float* d_Mp, float* d_Fd, float* d_Md, float* d_Jp, float* d_Jd, float abs_tol, float rel_tol,
+                       void* stream) {
+    return plant_step("pqp_plant_step_tol", p, B, d_x, d_D, d_Kp, warm, max_updates, d_Y, d_U, d_h, d_status, d_Fp,
+                      d_Mp, d_Fd, d_Md, d_Jp, d_Jd, abs_tol, rel_tol, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -2266,25 +2295,28 @@ int pqp_dynamics_advance(const pqp_dynamics* d, int B, const float* d_x, const f
 
 int pqp_plant_rollout_fused(int N, int M, int nd, int ns) { return plant_roll_shape_ok(N, M, nd, ns) ? 1 : 0; }
 
-int pqp_plant_rollout(pqp_plant* p, const pqp_dynamics* dyn, int B, int K, float* d_X, const float* d_D, int D_steps,
-                      const float* d_Kp, int warm, float y_floor, long long max_updates, float* d_Y, float* d_U,
-                      long long* d_h, int* d_status, float* d_Jp, float* d_Jd, void* stream) {
-    if (!p) return set_error(PQP_ERR_ARG, "pqp_plant_rollout: null plant");
-    if (!dyn) return set_error(PQP_ERR_ARG, "pqp_plant_rollout: null dynamics");
-    if (B <= 0) return set_error(PQP_ERR_ARG, "pqp_plant_rollout: B = %d states", B);
-    if (K <= 0) return set_error(PQP_ERR_ARG, "pqp_plant_rollout: K = %d steps", K);
+// pqp_plant_rollout (tolerances 0, 0) and pqp_plant_rollout_tol
+static int plant_rollout(const char* fn, pqp_plant* p, const pqp_dynamics* dyn, int B, int K, float* d_X,
+                         const float* d_D, int D_steps, const float* d_Kp, int warm, float y_floor,
+                         long long max_updates, float* d_Y, float* d_U, long long* d_h, int* d_status, float* d_Jp,
+                         float* d_Jd, float abs_tol, float rel_tol, void* stream) {
+    PQP_TRY(check_tols(fn, abs_tol, rel_tol));
+    if (!p) return set_error(PQP_ERR_ARG, "%s: null plant", fn);
+    if (!dyn) return set_error(PQP_ERR_ARG, "%s: null dynamics", fn);
+    if (B <= 0) return set_error(PQP_ERR_ARG, "%s: B = %d states", fn, B);
+    if (K <= 0) return set_error(PQP_ERR_ARG, "%s: K = %d steps", fn, K);
     if (D_steps != 1 && D_steps != K)
-        return set_error(PQP_ERR_ARG, "pqp_plant_rollout: D_steps = %d is neither 1 nor K = %d", D_steps, K);
-    if (!d_X || !d_D || !d_Y || !d_U) return set_error(PQP_ERR_ARG, "pqp_plant_rollout: null d_X, d_D, d_Y or d_U");
+        return set_error(PQP_ERR_ARG, "%s: D_steps = %d is neither 1 nor K = %d", fn, D_steps, K);
+    if (!d_X || !d_D || !d_Y || !d_U) return set_error(PQP_ERR_ARG, "%s: null d_X, d_D, d_Y or d_U", fn);
     const long long cap = pqp::batch_chunk_for(p->N, p->M);
     if (max_updates < 1 || max_updates > cap)
-        return set_error(PQP_ERR_ARG, "pqp_plant_rollout: max_updates = %lld is outside 1 .. %lld (pqp_plant_max_updates: "
-                                      "one step's budget)", max_updates, cap);
+        return set_error(PQP_ERR_ARG, "%s: max_updates = %lld is outside 1 .. %lld (pqp_plant_max_updates: "
+                                      "one step's budget)", fn, max_updates, cap);
     if (dyn->ns != p->ns || dyn->M != p->M || dyn->nd != p->nd)
-        return set_error(PQP_ERR_ARG, "pqp_plant_rollout: the dynamics' (ns=%d, M=%d, nd=%d) are not the plant's "
-                                      "(ns=%d, M=%d, nd=%d)", dyn->ns, dyn->M, dyn->nd, p->ns, p->M, p->nd);
+        return set_error(PQP_ERR_ARG, "%s: the dynamics' (ns=%d, M=%d, nd=%d) are not the plant's "
+                                      "(ns=%d, M=%d, nd=%d)", fn, dyn->ns, dyn->M, dyn->nd, p->ns, p->M, p->nd);
     if (dyn->dev != p->dev)
-        return set_error(PQP_ERR_ARG, "pqp_plant_rollout: the dynamics are on device %d, the plant on device %d", dyn->dev,
+        return set_error(PQP_ERR_ARG, "%s: the dynamics are on device %d, the plant on device %d", fn, dyn->dev,
                          p->dev);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t B_ = (size_t)B;
@@ -2293,6 +2325,7 @@ int pqp_plant_rollout(pqp_plant* p, const pqp_dynamics* dyn, int B, int K, float
     S.max_updates = max_updates;
     S.Kp = d_Kp;
     S.Y = d_Y;
+    S.abs_tol = abs_tol, S.rel_tol = rel_tol;
     DeviceGuard on(p->dev);
     if (p->kind == 1 && p->roll_slots > 0 && !g_plant_roll_chain) {  // ONE launch: k_plant_step's ROLL form
         S.warm = warm ? 1 : 0;
@@ -2321,6 +2354,21 @@ int pqp_plant_rollout(pqp_plant* p, const pqp_dynamics* dyn, int B, int K, float
         PQP_HIP(launch_plant_advance(dyn->data, a, s));
     }
     return PQP_OK;
+}
+
+int pqp_plant_rollout(pqp_plant* p, const pqp_dynamics* dyn, int B, int K, float* d_X, const float* d_D, int D_steps,
+                      const float* d_Kp, int warm, float y_floor, long long max_updates, float* d_Y, float* d_U,
+                      long long* d_h, int* d_status, float* d_Jp, float* d_Jd, void* stream) {
+    return plant_rollout("pqp_plant_rollout", p, dyn, B, K, d_X, d_D, D_steps, d_Kp, warm, y_floor, max_updates, d_Y,
+                         d_U, d_h, d_status, d_Jp, d_Jd, 0.0f, 0.0f, stream);
+}
+
+int pqp_plant_rollout_tol(pqp_plant* p, const pqp_dynamics* dyn, int B, int K, float* d_X, const float* d_D,
+                          int D_steps, const float* d_Kp, int warm, float y_floor, long long max_updates, float* d_Y,
+                          float* d_U, long long* d_h, int* d_status, float* d_Jp, float* d_Jd, float abs_tol,
+                          float rel_tol, void* stream) {
+    return plant_rollout("pqp_plant_rollout_tol", p, dyn, B, K, d_X, d_D, D_steps, d_Kp, warm, y_floor, max_updates,
+                         d_Y, d_U, d_h, d_status, d_Jp, d_Jd, abs_tol, rel_tol, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -2480,13 +2528,16 @@ int pqp_shared_relinearize(pqp_shared* p, int B, const float* d_Fp, const float*
     return PQP_OK;
 }
 
-int pqp_shared_solve(pqp_shared* p, int B, const float* d_Fd, const float* d_Md, const float* d_Fp, const float* d_Mp,
-                     const float* d_Kp, long long max_updates, const float* d_Y0, float* d_Y, float* d_U,
-                     long long* d_h, int* d_status, float* d_Jp, float* d_Jd, void* stream) {
-    if (!p) return set_error(PQP_ERR_ARG, "pqp_shared_solve: null handle");
-    if (B <= 0) return set_error(PQP_ERR_ARG, "pqp_shared_solve: B = %d states", B);
+// pqp_shared_solve (tolerances 0, 0) and pqp_shared_solve_tol
+static int shared_solve(const char* fn, pqp_shared* p, int B, const float* d_Fd, const float* d_Md, const float* d_Fp,
+                        const float* d_Mp, const float* d_Kp, long long max_updates, const float* d_Y0, float* d_Y,
+                        float* d_U, long long* d_h, int* d_status, float* d_Jp, float* d_Jd, float abs_tol,
+                        float rel_tol, void* stream) {
+    PQP_TRY(check_tols(fn, abs_tol, rel_tol));
+    if (!p) return set_error(PQP_ERR_ARG, "%s: null handle", fn);
+    if (B <= 0) return set_error(PQP_ERR_ARG, "%s: B = %d states", fn, B);
     if (!d_Fd || !d_Md || !d_Fp || !d_Mp || !d_Y || !d_U)
-        return set_error(PQP_ERR_ARG, "pqp_shared_solve: null d_Fd, d_Md, d_Fp, d_Mp, d_Y or d_U");
+        return set_error(PQP_ERR_ARG, "%s: null d_Fd, d_Md, d_Fp, d_Mp, d_Y or d_U", fn);
     DeviceGuard on(p->dev);
     PQP_TRY(ensure_device());
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -2503,6 +2554,7 @@ int pqp_shared_solve(pqp_shared* p, int B, const float* d_Fd, const float* d_Md,
     a.pending = static_cast<int*>(pending.p);
     a.N = p->N, a.M = p->M, a.ldq = p->ldq, a.ldm = p->ldm, a.B = B, a.sym = p->sym;
     a.max_updates = max_updates;
+    a.abs_tol = abs_tol, a.rel_tol = rel_tol;
     a.chunk = pqp::batch_chunk_for(p->N, p->M);
     PQP_HIP(launch_shared_solve_init(B, p->N, a.st, d_Y0, d_Y, s));
     for (;;) {  // bounded launches that resume from the device state
@@ -2514,6 +2566,21 @@ int pqp_shared_solve(pqp_shared* p, int B, const float* d_Fd, const float* d_Md,
         if (left == 0) break;
     }
     return PQP_OK;
+}
+
+int pqp_shared_solve(pqp_shared* p, int B, const float* d_Fd, const float* d_Md, const float* d_Fp, const float* d_Mp,
+                     const float* d_Kp, long long max_updates, const float* d_Y0, float* d_Y, float* d_U,
+                     long long* d_h, int* d_status, float* d_Jp, float* d_Jd, void* stream) {
+    return shared_solve("pqp_shared_solve", p, B, d_Fd, d_Md, d_Fp, d_Mp, d_Kp, max_updates, d_Y0, d_Y, d_U, d_h,
+                        d_status, d_Jp, d_Jd, 0.0f, 0.0f, stream);
+}
+
+int pqp_shared_solve_tol(pqp_shared* p, int B, const float* d_Fd, const float* d_Md, const float* d_Fp,
+                         const float* d_Mp, const float* d_Kp, long long max_updates, const float* d_Y0, float* d_Y,
+                         float* d_U, long long* d_h, int* d_status, float* d_Jp, float* d_Jd, float abs_tol,
+                         float rel_tol, void* stream) {
+    return shared_solve("pqp_shared_solve_tol", p, B, d_Fd, d_Md, d_Fp, d_Mp, d_Kp, max_updates, d_Y0, d_Y, d_U, d_h,
+                        d_status, d_Jp, d_Jd, abs_tol, rel_tol, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -2534,28 +2601,32 @@ long long pqp_shared_max_updates(const pqp_shared* p) {
     return pqp::batch_chunk_for(p->N, p->M);
 }
 
-int pqp_shared_step(pqp_shared* p, int B, const float* d_x, const float* d_D, const float* d_Kp, int warm,
-                    long long max_updates, float* d_Y, float* d_U, long long* d_h, int* d_status, float* d_Fp,
-                    float* d_Mp, float* d_Fd, float* d_Md, float* d_Jp, float* d_Jd, void* stream) {
-    if (!p) return set_error(PQP_ERR_ARG, "pqp_shared_step: null handle");
-    if (B <= 0) return set_error(PQP_ERR_ARG, "pqp_shared_step: B = %d states", B);
+// pqp_shared_step (tolerances 0, 0) and pqp_shared_step_tol
+static int shared_step(const char* fn, pqp_shared* p, int B, const float* d_x, const float* d_D, const float* d_Kp,
+                       int warm, long long max_updates, float* d_Y, float* d_U, long long* d_h, int* d_status,
+                       float* d_Fp, float* d_Mp, float* d_Fd, float* d_Md, float* d_Jp, float* d_Jd, float abs_tol,
+                       float rel_tol, void* stream) {
+    PQP_TRY(check_tols(fn, abs_tol, rel_tol));
+    if (!p) return set_error(PQP_ERR_ARG, "%s: null handle", fn);
+    if (B <= 0) return set_error(PQP_ERR_ARG, "%s: B = %d states", fn, B);
     if (!d_x || !d_D || !d_Y || !d_U || !d_Fp || !d_Fd)
-        return set_error(PQP_ERR_ARG, "pqp_shared_step: null d_x, d_D, d_Y, d_U, d_Fp or d_Fd");
+        return set_error(PQP_ERR_ARG, "%s: null d_x, d_D, d_Y, d_U, d_Fp or d_Fd", fn);
     if (p->nd == 0)
-        return set_error(PQP_ERR_ARG, "pqp_shared_step: the handle was made by pqp_shared_create and has no plant "
-                                      "matrices (use pqp_shared_create_plant)");
+        return set_error(PQP_ERR_ARG, "%s: the handle was made by pqp_shared_create and has no plant "
+                                      "matrices (use pqp_shared_create_plant)", fn);
     const long long cap = pqp::batch_chunk_for(p->N, p->M);
     if (max_updates < 1 || max_updates > cap)
-        return set_error(PQP_ERR_ARG, "pqp_shared_step: max_updates = %lld is outside 1 .. %lld "
-                                      "(pqp_shared_max_updates: one launch's budget)", max_updates, cap);
+        return set_error(PQP_ERR_ARG, "%s: max_updates = %lld is outside 1 .. %lld "
+                                      "(pqp_shared_max_updates: one launch's budget)", fn, max_updates, cap);
     SharedStepArgs t{};
-    SharedSolveArgs& a = t.solve;
+    SharedSolveCore& a = t.solve;
     a.QdR = p->QdR.f(), a.QdT = p->sym ? p->QdR.f() : p->QdT.f(), a.theta = p->theta.f();
     a.GpP = p->GpP.f(), a.GpT = p->GpT.f(), a.QinvT = p->QinvT.f(), a.QpP = p->QpP.f(), a.Kp = p->Kp.f();
     a.Fd = d_Fd, a.Fp = d_Fp, a.KpB = d_Kp;  // Md, Mp: the kernel's own words
     a.Y = d_Y, a.U = d_U, a.h = d_h, a.status = d_status, a.Jp = d_Jp, a.Jd = d_Jd;
     a.N = p->N, a.M = p->M, a.ldq = p->ldq, a.ldm = p->ldm, a.B = B, a.sym = p->sym;
     a.max_updates = max_updates;
+    t.abs_tol = abs_tol, t.rel_tol = rel_tol;
     a.chunk = max_updates;  // every state finishes within it
     t.Fp1T = p->Fp1T.f(), t.Fp2T = p->Fp2T.f(), t.Fp3 = p->Fp3.f();
     t.Mp1P = p->Mp1P.f(), t.Mp2P = p->Mp2P.f(), t.Mp3P = p->Mp3P.f();
@@ -2567,6 +2638,26 @@ int pqp_shared_step(pqp_shared* p, int B, const float* d_x, const float* d_D, co
     PQP_HIP(launch_step_shared(t, p->S, static_cast<hipStream_t>(stream)));
     return PQP_OK;
 }
+
+int pqp_shared_step(pqp_shared* p, int B, const float* d_x, const float* d_D, const float* d_Kp, int warm,
+                    long long max_updates, float* d_Y, float* d_U, long long* d_h, int* d_status, float* d_Fp,
+                    float* d_Mp, float* d_Fd, float* d_Md, float* d_Jp, float* d_Jd, void* stream) {
+    return shared_step("pqp_shared_step", p, B, d_x, d_D, d_Kp, warm, max_updates, d_Y, d_U, d_h, d_status, d_Fp, d_Mp,
+                       d_Fd, d_Md, d_Jp, d_Jd, 0.0f, 0.0f, stream);
+}
+
+int pqp_shared_step_tol(pqp_shared* p, int B, const float* d_x, const float* d_D, const float* d_Kp, int warm,
+                        long long max_updates, float* d_Y, float* d_U, long long* d_h, int* d_status, float* d_Fp,
+                        float* d_Mp, float* d_Fd, float* d_Md, float* d_Jp, float* d_Jd, float abs_tol, float rel_tol,
+                        void* stream) {
+    return shared_step("pqp_shared_step_tol", p, B, d_x, d_D, d_Kp, warm, max_updates, d_Y, d_U, d_h, d_status, d_Fp,
+                       d_Mp, d_Fd, d_Md, d_Jp, d_Jd, abs_tol, rel_tol, stream);
+}
+
+// ---------------------------------------------------------------------------
+// 2k. the gap-tolerance stopping rule: the predicate itself, on the host
+// ---------------------------------------------------------------------------
+int pqp_stop_decide(float Jp, float Jd, float abs_tol, float rel_tol) { return pqp::stop_decide(Jp, Jd, abs_tol, rel_tol); }
 
 // ---------------------------------------------------------------------------
 // 1. drop-in entry points (reference signatures)

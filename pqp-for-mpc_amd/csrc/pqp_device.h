@@ -30,6 +30,29 @@ __host__ __device__ __forceinline__ bool gap_stop(float Jp, float Jd) {
     return !(gap / fabs((double)Jd) > kTol);
 }
 
+// The caller's gap tolerances (pqp.h 2k), tried only where gap_stop said
+// continue.  At the plants' costs (|Jd| about 1.5e5: one float32 ulp is
+// 0.0156) the reference's 1e-6 never decides, so a gap that settles one ulp
+// above zero never stops; these let the caller say how small is small enough.
+// gap: the float32 sum, as :683.  One double product, no division.  A NaN gap
+// (or a NaN Jd) matches neither test.  3: stop, within the tolerances.
+__host__ __device__ __forceinline__ int tol_stop(float Jp, float Jd, float abs_tol, float rel_tol) {
+    if (!(abs_tol > 0) && !(rel_tol > 0)) return 0;
+    const double gap = (double)(Jp + Jd);
+    if (gap <= (double)abs_tol) return 3;
+    if (gap <= (double)rel_tol * fabs((double)Jd)) return 3;
+    return 0;
+}
+// 0 continue, 1 the reference's tests pass (:682-685), 3 within the caller's
+// tolerances.  The reference's test first: a tolerance can only stop a solve
+// earlier, and with both 0 the decision is gap_stop's alone.  The kernels
+// spell the two halves out at their one call site each (gap_stop, then
+// tol_stop where it said continue); pqp_stop_decide is this function.
+__host__ __device__ __forceinline__ int stop_decide(float Jp, float Jd, float abs_tol, float rel_tol) {
+    if (gap_stop(Jp, Jd)) return 1;
+    return tol_stop(Jp, Jd, abs_tol, rel_tol);
+}
+
 // ---------------------------------------------------------------------------
 // Relay hand-off wait (k_split_relay, k_lean_relay, k_gemv_relay): spin until
 // every lane's 64-bit LDS word {sequence, bits(running sum)} carries sequence

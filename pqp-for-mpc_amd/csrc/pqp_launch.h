@@ -6,7 +6,8 @@
 
 namespace pqp {
 
-enum SolveStatus : int { kStatusContinue = 0, kStatusDone = 1, kStatusCapped = 2 };
+// kStatusTol: stopped within the caller's gap tolerances (pqp.h 2k; the plant family's kernels only)
+enum SolveStatus : int { kStatusContinue = 0, kStatusDone = 1, kStatusCapped = 2, kStatusTol = 3 };
 // SolveArgs::mode: 0 converge, 1 fixed, 2 evaluate terminate() once (no update)
 enum SolveMode : int { kModeConverge = 0, kModeFixed = 1, kModeTerminate = 2 };
 

@@ -25,7 +25,11 @@ struct PlantStep {
     long long* h;
     int* status;
     float *Fp, *Mp, *Fd, *Md, *Jp, *Jd;
+    float abs_tol, rel_tol;  // the gap tolerances (pqp.h 2k); both 0: the reference's rule alone
 };
+// A step with a positive tolerance runs the kernels' _tol build (k_plant_step_tol, k_plant_step_mid_tol); every
+// other step the build without the tolerances, whose instructions are those it had before them.
+inline bool plant_step_tol(const PlantStep& S) { return S.abs_tol > 0.0f || S.rel_tol > 0.0f; }
 
 // Test and tuning knobs of the step (pqp_tune keys "plant_grid", "plant_pipe").
 // plant_grid: at most this many workgroups (0: every resident wave slot);

@@ -40,7 +40,7 @@ struct SharedSolveState {
 //   QdR  [N][ldq] row-major Qd (Y'Qd)          GpP  [N][ldm] row-major Gp (Gp'Y)
 //   GpT  [M][ldq] Gp' (checkFeas)              QinvT [M][ldm] Qp_inv' (U)
 //   QpP  [M][ldm] row-major Qp (U'Qp)
-struct SharedSolveArgs {
+struct SharedSolveCore {
     const float *QdT, *QdR, *theta, *GpP, *GpT, *QinvT, *QpP, *Kp;
     const float *Fd, *Md, *Fp, *Mp, *KpB;  // per state: [B][N], [B], [B][M], [B], NULL or [B][N]
     float *Y, *U;                          // [B][N] (in: the iterate to continue from), [B][M]
@@ -52,6 +52,15 @@ struct SharedSolveArgs {
     int N, M, ldq, ldm, B, sym;
     long long max_updates, chunk;
 };
+// k_solve_shared's argument: the above, then the gap tolerances (pqp.h 2k; both 0: the reference's rule alone).
+// They come last here and in SharedStepArgs, which embeds the core without them, so that every word the kernels
+// read before the tolerances existed keeps its place in the kernel arguments.
+struct SharedSolveArgs : SharedSolveCore {
+    float abs_tol, rel_tol;
+};
+// A solve or step with a positive tolerance runs the kernels' _tol build (k_solve_shared_tol, k_step_shared_tol);
+// every other one the build without the tolerances, whose instructions are those it had before them.
+inline bool shared_tol(float abs_tol, float rel_tol) { return abs_tol > 0.0f || rel_tol > 0.0f; }
 // st[b] = {h = 1, running, no costs}; Y[b] = Y0[b] (NULL: 1000; Y itself: kept)
 hipError_t launch_shared_solve_init(int B, int N, SharedSolveState* st, const float* Y0, float* Y, hipStream_t s);
 // one bounded launch: every running state advances by at most a.chunk iterates
@@ -92,12 +101,13 @@ int step_shared_states(int N, int M, int nd, int ns);
 //   GQT, QinvR as SharedRelinArgs;  Fp3 [M], Mp4 [ns], Mp5 [nd], Mp6 [1] as given
 // (ldx = round4(ns), ldd = round4(nd)).
 struct SharedStepArgs {
-    SharedSolveArgs solve;
+    SharedSolveCore solve;
     const float *Fp1T, *Fp2T, *Fp3, *Mp1P, *Mp2P, *Mp3P, *Mp4, *Mp5, *Mp6, *GQT, *QinvR;
     const float *x, *D;  // [B][ns], [B][nd]
     float *Fp, *Fd;      // [B][M], [B][N]: outputs, and what the solve loop reads
     float *Mp, *Md;      // [B] each, optional
     int nd, ns, warm;
+    float abs_tol, rel_tol;  // the gap tolerances (pqp.h 2k), last: see SharedSolveArgs
 };
 // one launch: every state runs to its end (max_updates <= one launch's budget)
 hipError_t launch_step_shared(const SharedStepArgs& a, int S, hipStream_t s);

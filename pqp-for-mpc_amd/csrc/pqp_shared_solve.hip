@@ -16,7 +16,7 @@
 //                infeasible iff some row has sum_j Gp[i][j] U_j > Kp_i + max_ref((float)(1e-6 Kp_i), (float)1e-6);
 //                else Jd from tq_j = sum_i y_i Qd[i][j], quad = sum_j tq_j y_j, lin = sum_j Fd_j y_j,
 //                J = (float)(0.0 + 0.5 (double)quad); J += lin; J += Md / 2; Jp the same with U, Qp, Fp, Mp;
-//                then gap_stop(Jp, Jd).
+//                then gap_stop(Jp, Jd) and, where it says continue, the caller's tolerances (tol_stop, pqp.h 2k).
 //
 // One workgroup owns S consecutive states.  Every per-state vector lives in
 // LDS as [index][S]: a product against a shared matrix reads its S operands of
@@ -200,7 +200,7 @@ __device__ __forceinline__ void upd_segment(UpdAcc<S, FUSE>& a, const float* __r
 
 // updateY2 (PQP_CPU.c:603-618) of the workgroup's S states from `cur` into `nxt`; FUSE: tq = Y'Qd of `cur` too
 template <int S, bool FUSE>
-__device__ __forceinline__ void shared_update(const SharedSolveArgs& A, int b0, int ns, const float* __restrict__ cur,
+__device__ __forceinline__ void shared_update(const SharedSolveCore& A, int b0, int ns, const float* __restrict__ cur,
                                               float* __restrict__ nxt, float* __restrict__ tq) {
     const int N = A.N, ldq = A.ldq;
     const int tid = threadIdx.x, NT = blockDim.x, wave = tid >> 6;
@@ -290,10 +290,12 @@ struct SharedSolveCtl {
 // md / mp: Md and Mp of state s at [s].  A state that finishes has its Y, U, h, status and costs
 // written at that moment (RESUME: its resume words too).  Leaves when no state is running or
 // A.chunk updates were made; returns the states still running, `cur` the image of their iterate.
-template <int S, bool RESUME>
-__device__ __forceinline__ int shared_converge_loop(const SharedSolveArgs& A, int b0, int ns, float* lds,
+// TOL: the caller's gap tolerances abs_tol, rel_tol (pqp.h 2k) are tried where gap_stop says continue; else
+// they are not read.
+template <int S, bool RESUME, bool TOL>
+__device__ __forceinline__ int shared_converge_loop(const SharedSolveCore& A, int b0, int ns, float* lds,
                                                     const SharedSolveCtl& c, const float* md, const float* mp,
-                                                    float*& cur) {
+                                                    float*& cur, float abs_tol, float rel_tol) {
     const int tid = threadIdx.x, NT = blockDim.x;
     const int N = A.N, M = A.M, ldq = A.ldq, ldm = A.ldm;
     long long* const s_h = c.h;
@@ -378,13 +380,16 @@ __device__ __forceinline__ int shared_converge_loop(const SharedSolveArgs& A, in
             int fresh = 0;
             if (s_fin[s] == kStatusContinue) {
                 bool stop = false;
+                int how = kStatusDone;  // TOL: or kStatusTol
                 if (!s_bad[s]) {
                     const float Jp = s_jp[s], Jd = s_jd[s];
                     s_Jp[s] = Jp, s_Jd[s] = Jd;
                     stop = gap_stop(Jp, Jd);
+                    if constexpr (TOL)
+                        if (!stop && tol_stop(Jp, Jd, abs_tol, rel_tol)) stop = true, how = kStatusTol;
                 }
                 const long long h = s_h[s];
-                const int fin = stop ? kStatusDone
+                const int fin = stop ? how
                                      : (A.max_updates > 0 && h - 1 >= A.max_updates) ? kStatusCapped : kStatusContinue;
                 if (fin != kStatusContinue) {
                     s_fin[s] = fin;
@@ -422,53 +427,18 @@ __device__ __forceinline__ int shared_converge_loop(const SharedSolveArgs& A, in
 
 }  // namespace
 
-// grid = ceil(B / S) workgroups of blockDim.x (a multiple of 64) threads;
-// dynamic LDS = S * solve_shared_state_floats(N, M) floats.
-template <int S>
-__global__ void __launch_bounds__(kSolveSharedThreads) k_solve_shared(SharedSolveArgs A) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    __shared__ long long s_h[S];
-    __shared__ int s_fin[S], s_bad[S], s_new[S];
-    __shared__ float s_Jp[S], s_Jd[S], s_jp[S], s_jd[S];
-    const int tid = threadIdx.x, NT = blockDim.x;
-    const int N = A.N, ldq = A.ldq;
-    const int b0 = blockIdx.x * S;
-    const int ns = (A.B - b0) < S ? (A.B - b0) : S;  // states of this block
-    if (tid < S) {
-        SharedSolveState z;
-        z.h = 0, z.status = kStatusDone, z.Jp = z.Jd = 0.0f;  // a missing state: finished, never written
-        if (tid < ns) z = A.st[b0 + tid];
-        s_h[tid] = z.h, s_fin[tid] = z.status, s_Jp[tid] = z.Jp, s_Jd[tid] = z.Jd;
-        s_bad[tid] = s_new[tid] = 0;
-    }
-    int left = __syncthreads_count(tid < S && s_fin[tid] == kStatusContinue);
-    if (left == 0) return;  // every state finished in an earlier launch
-    float* ya = lds;                   // [ldq][S]
-    float* yb = ya + (size_t)S * ldq;  // [ldq][S]
-    for (int s = 0; s < S; ++s) {
-        const float* y0 = (s < ns && s_fin[s] == kStatusContinue) ? A.Y + (size_t)(b0 + s) * N : nullptr;
-        for (int i = tid; i < ldq; i += NT) {
-            ya[(size_t)i * S + s] = (y0 && i < N) ? y0[i] : 0.0f;
-            yb[(size_t)i * S + s] = 0.0f;
-        }
-    }
-    __syncthreads();
-    const SharedSolveCtl ctl = {s_h, s_fin, s_bad, s_new, s_Jp, s_Jd, s_jp, s_jd};
-    float* cur;
-    left = shared_converge_loop<S, true>(A, b0, ns, lds, ctl, A.Md + b0, A.Mp + b0, cur);
-    if (left == 0) return;
-    // the states still running: their iterate and resume words for the next launch
-    for (int s = 0; s < ns; ++s) {
-        if (s_fin[s] != kStatusContinue) continue;
-        for (int i = tid; i < N; i += NT) A.Y[(size_t)(b0 + s) * N + i] = cur[(size_t)i * S + s];
-    }
-    if (tid < ns && s_fin[tid] == kStatusContinue) {
-        SharedSolveState z;
-        z.h = s_h[tid], z.status = kStatusContinue, z.pad = 0, z.Jp = s_Jp[tid], z.Jd = s_Jd[tid];
-        A.st[b0 + tid] = z;
-    }
-    if (tid == 0 && A.pending) atomicAdd(A.pending, 1);
-}
+// k_solve_shared and k_solve_shared_tol: one text (pqp_shared_solve_kernel.inc), compiled with and without the
+// caller's gap tolerances (pqp.h 2k)
+#define PQP_SOLVE_SHARED_KERNEL k_solve_shared
+#define PQP_SOLVE_SHARED_TOL false
+#include "pqp_shared_solve_kernel.inc"
+#undef PQP_SOLVE_SHARED_KERNEL
+#undef PQP_SOLVE_SHARED_TOL
+#define PQP_SOLVE_SHARED_KERNEL k_solve_shared_tol
+#define PQP_SOLVE_SHARED_TOL true
+#include "pqp_shared_solve_kernel.inc"
+#undef PQP_SOLVE_SHARED_KERNEL
+#undef PQP_SOLVE_SHARED_TOL
 
 // Fd [B][N] and Md [B] of B states (convertToDual's computeFd / computeMd, PQP_CPU.c:456-479; pqp_relin.hip's
 // arithmetic) against the shared Gp Qp_inv and Qp_inv: one workgroup per S states, Fp staged as [k][S].
@@ -554,6 +524,14 @@ hipError_t launch_solve_shared(const SharedSolveArgs& a, int S, hipStream_t s) {
     if (S != solve_shared_states(a.N, a.M) || S == 0) return hipErrorInvalidValue;
     const size_t lds = solve_shared_lds_bytes(a.N, a.M, S);
     const dim3 grid((unsigned)((a.B + S - 1) / S)), block(solve_shared_threads(a.N, a.M));
+    if (shared_tol(a.abs_tol, a.rel_tol)) {  // a positive tolerance: the _tol build
+        switch (S) {
+            case 8: hipLaunchKernelGGL(k_solve_shared_tol<8>, grid, block, lds, s, a); break;
+            case 4: hipLaunchKernelGGL(k_solve_shared_tol<4>, grid, block, lds, s, a); break;
+            default: hipLaunchKernelGGL(k_solve_shared_tol<2>, grid, block, lds, s, a); break;
+        }
+        return hipGetLastError();
+    }
     switch (S) {
         case 8: hipLaunchKernelGGL(k_solve_shared<8>, grid, block, lds, s, a); break;
         case 4: hipLaunchKernelGGL(k_solve_shared<4>, grid, block, lds, s, a); break;

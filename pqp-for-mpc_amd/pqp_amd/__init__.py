@@ -36,6 +36,8 @@ PQP_ERR_ARG, PQP_ERR_HIP, PQP_ERR_ALLOC, PQP_ERR_IO, PQP_ERR_NOT_CONVERGED, PQP_
 PQP_ERR_NEEDS_QDT = -7
 MODE_CONVERGE, MODE_FIXED = 0, 1
 START_COLD, START_HOST, START_LAST = 0, 1, 2
+# per-state status words of the plant family (include/pqp.h, section 2k)
+PQP_STATUS_DONE, PQP_STATUS_CAPPED, PQP_STATUS_TOL = 1, 2, 3
 
 # The reference's compile-time problem dimensions (PQP_CPU.c:13-17).
 P_HORIZON, N_STATE, N_INPUT, N_OUTPUT, N_DIS = 1, 29, 7, 7, 1
@@ -129,6 +131,15 @@ SIGNATURES = {
     "pqp_plant_rollout_fused": (C.c_int, [C.c_int] * 4),
     "pqp_plant_rollout": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.c_float,
                                     C.c_longlong] + [_vp] * 6 + [_vp]),
+    "pqp_stop_decide": (C.c_int, [C.c_float] * 4),
+    "pqp_plant_step_tol": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_longlong] + [_vp] * 10
+                           + [C.c_float, C.c_float, _vp]),
+    "pqp_plant_rollout_tol": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.c_float,
+                                        C.c_longlong] + [_vp] * 6 + [C.c_float, C.c_float, _vp]),
+    "pqp_shared_solve_tol": (C.c_int, [_vp, C.c_int] + [_vp] * 5 + [C.c_longlong] + [_vp] * 7
+                             + [C.c_float, C.c_float, _vp]),
+    "pqp_shared_step_tol": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_longlong] + [_vp] * 10
+                            + [C.c_float, C.c_float, _vp]),
     "pqp_rowblock_create": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, C.POINTER(C.c_void_p)]),
     "pqp_rowblock_update": (C.c_int, [_vp, _vp, _vp, _vp]),
     "pqp_rowblock_check": (C.c_int, [_vp, _vp]),
@@ -267,6 +278,13 @@ def last_error() -> str:
 def _check(rc: int):
     if rc != PQP_OK:
         raise PQPError(rc, last_error())
+
+
+def stop_decide(Jp: float, Jd: float, abs_tol: float = 0.0, rel_tol: float = 0.0) -> int:
+    """The plant family's stopping rule (pqp_stop_decide, include/pqp.h section
+    2k) for an iterate that passed checkFeas, on the host: 0 go on, 1 the
+    reference's own tests pass, 3 within the tolerances.  Needs no device."""
+    return int(lib().pqp_stop_decide(float(Jp), float(Jd), float(abs_tol), float(rel_tol)))
 
 
 def _f32(a) -> np.ndarray:
@@ -1023,7 +1041,8 @@ class Plant:
             raise ValueError(f"Plant.step: {what} must be [{self.B}, {cols}]")
         return t
 
-    def step(self, x, D=None, Kp=None, warm: bool = False, floor: float | None = None, max_updates: int | None = None):
+    def step(self, x, D=None, Kp=None, warm: bool = False, floor: float | None = None, max_updates: int | None = None,
+             abs_tol: float = 0.0, rel_tol: float = 0.0):
         """One control step at states ``x`` [B, ns] (numpy or a device tensor;
         a contiguous float32 tensor on the plant's device is used in place):
         fills the device tensors Y, U, h, status, Fp, Mp, Fd, Md, Jp, Jd and
@@ -1035,13 +1054,16 @@ class Plant:
         from the rows of ``self.Y`` (the previous step's, or what the caller
         put there) instead of Y = 1000.  floor: ``self.Y.clamp_min_(floor)``
         first, and warm (see ProblemBatch.solve).  max_updates: at most
-        ``self.max_updates`` (one launch's budget), the default."""
+        ``self.max_updates`` (one launch's budget), the default.  abs_tol,
+        rel_tol: also stop, with status 3, at a feasible iterate whose gap
+        Jp + Jd is <= abs_tol or <= rel_tol |Jd| (section 2k; both 0, the
+        default: the reference's rule alone)."""
         torch = self.torch
         f = dict(dtype=torch.float32, device=self.device)
         B = int(x.shape[0]) if hasattr(x, "shape") and len(x.shape) == 2 else len(x)
         if B != self.B or self._roll_K:  # (after a rollout the outputs carry its K axis: made anew, Y kept)
             if B <= 0:
-                _check(lib().pqp_plant_step(self._h, B, *([None] * 3), 0, 1, *([None] * 10), None))
+                _check(lib().pqp_plant_step_tol(self._h, B, *([None] * 3), 0, 1, *([None] * 10), 0.0, 0.0, None))
             Y = self.Y if B == self.B else torch.zeros(B, self.N, **f)
             self.B, self._roll_K = B, 0
             self.Y, self.U = Y, torch.zeros(B, self.M, **f)
@@ -1067,8 +1089,8 @@ class Plant:
         cap = self.max_updates if max_updates is None else int(max_updates)
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         self._inputs = (xt, Dt, Kt)  # alive until the next step: the launch is asynchronous
-        _check(lib().pqp_plant_step(self._h, B, p(xt), p(Dt), None if Kt is None else p(Kt), int(bool(warm)), cap,
-                                    *[p(getattr(self, k)) for k in self.OUT], stream))
+        _check(lib().pqp_plant_step_tol(self._h, B, p(xt), p(Dt), None if Kt is None else p(Kt), int(bool(warm)), cap,
+                                        *[p(getattr(self, k)) for k in self.OUT], float(abs_tol), float(rel_tol), stream))
         return self
 
     @staticmethod
@@ -1077,7 +1099,8 @@ class Plant:
         return bool(lib().pqp_plant_rollout_fused(int(N), int(M), int(nd), int(ns)))
 
     def rollout(self, x0, K: int, dynamics: "Dynamics", D=None, Kp=None, warm: bool = False,
-                floor: float | None = None, max_updates: int | None = None):
+                floor: float | None = None, max_updates: int | None = None, abs_tol: float = 0.0,
+                rel_tol: float = 0.0):
         """K control steps of the states ``x0`` [B, ns] under ``dynamics``
         (pqp_plant_rollout, section 2j): step, x+ = (A x + Bu U) + Bd D, warm
         step, ... without leaving the device -- one launch for the one-wave
@@ -1091,13 +1114,15 @@ class Plant:
         Kp [B, N] or None, constant over the steps.  warm: step 0 starts from
         the rows of ``self.Y``; later steps always start from the previous
         step's Y.  floor: Y is floored before every warm start (unlike
-        ``step``'s, it does not make step 0 warm).  max_updates: per step."""
+        ``step``'s, it does not make step 0 warm).  max_updates: per step.
+        abs_tol, rel_tol: ``step``'s gap tolerances, at every step."""
         torch = self.torch
         f = dict(dtype=torch.float32, device=self.device)
         K = int(K)
         B = int(x0.shape[0]) if hasattr(x0, "shape") and len(x0.shape) == 2 else len(x0)
         if B <= 0 or K <= 0:
-            _check(lib().pqp_plant_rollout(self._h, dynamics._h, B, K, None, None, 1, None, 0, 0.0, 1, *([None] * 6), None))
+            _check(lib().pqp_plant_rollout_tol(self._h, dynamics._h, B, K, None, None, 1, None, 0, 0.0, 1, *([None] * 6),
+                                               0.0, 0.0, None))
         if B != self.B or self._roll_K != K:
             keep_Y = B == self.B
             self.B, self._roll_K = B, K
@@ -1127,9 +1152,10 @@ class Plant:
         cap = self.max_updates if max_updates is None else int(max_updates)
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         self._inputs = (Dt, Kt, dynamics)  # alive until the next call: the launches are asynchronous
-        _check(lib().pqp_plant_rollout(self._h, dynamics._h, B, K, p(self.X), p(Dt), d_steps, None if Kt is None else p(Kt),
-                                       int(bool(warm)), 0.0 if floor is None else float(floor), cap, p(self.Y), p(self.U),
-                                       p(self.h), p(self.status), p(self.Jp), p(self.Jd), stream))
+        _check(lib().pqp_plant_rollout_tol(self._h, dynamics._h, B, K, p(self.X), p(Dt), d_steps,
+                                           None if Kt is None else p(Kt), int(bool(warm)),
+                                           0.0 if floor is None else float(floor), cap, p(self.Y), p(self.U), p(self.h),
+                                           p(self.status), p(self.Jp), p(self.Jd), float(abs_tol), float(rel_tol), stream))
         return self
 
     def close(self):
@@ -1280,11 +1306,14 @@ class SharedProblem:
         self._relin_inputs = (Fp, Mp, Kt)  # alive until the next call: the launch is asynchronous
         return Fd, Md
 
-    def solve(self, Fd, Md, Fp, Mp, Kp=None, Y0=None, max_updates: int = 0):
+    def solve(self, Fd, Md, Fp, Mp, Kp=None, Y0=None, max_updates: int = 0, abs_tol: float = 0.0,
+              rel_tol: float = 0.0):
         """The converge solve of B states: fills the device tensors Y [B, N],
         U [B, M], h (int64), status (1 converged, 2 hit max_updates), Jp, Jd and
         returns self.  Y0 [B, N]: the start (None: Y = 1000; ``self.Y`` itself:
-        in place).  max_updates <= 0: no cap.  Synchronous."""
+        in place).  max_updates <= 0: no cap.  abs_tol, rel_tol: the gap
+        tolerances of section 2k (status 3; both 0: the reference's rule alone).
+        Synchronous."""
         torch = self.torch
         p = ProblemBatch._p
         f = dict(dtype=torch.float32, device=self.device)
@@ -1301,9 +1330,10 @@ class SharedProblem:
             self.h = torch.zeros(B, dtype=torch.int64, device=self.device)
             self.status = torch.zeros(B, dtype=torch.int32, device=self.device)
             self.Jp, self.Jd = torch.zeros(B, **f), torch.zeros(B, **f)
-        _check(lib().pqp_shared_solve(self._h, B, p(Fd), p(Md), p(Fp), p(Mp), None if Kt is None else p(Kt),
-                                      int(max_updates), None if Y0t is None else p(Y0t), p(self.Y), p(self.U),
-                                      p(self.h), p(self.status), p(self.Jp), p(self.Jd), self._stream()))
+        _check(lib().pqp_shared_solve_tol(self._h, B, p(Fd), p(Md), p(Fp), p(Mp), None if Kt is None else p(Kt),
+                                          int(max_updates), None if Y0t is None else p(Y0t), p(self.Y), p(self.U),
+                                          p(self.h), p(self.status), p(self.Jp), p(self.Jd), float(abs_tol),
+                                          float(rel_tol), self._stream()))
         return self
 
     def close(self):
@@ -1380,7 +1410,8 @@ class SharedPlant(SharedProblem):
             raise ValueError(f"SharedPlant.step: {what} must be [{self.B}, {cols}]")
         return t
 
-    def step(self, x, D=None, Kp=None, warm: bool = False, floor: float | None = None, max_updates: int | None = None):
+    def step(self, x, D=None, Kp=None, warm: bool = False, floor: float | None = None, max_updates: int | None = None,
+             abs_tol: float = 0.0, rel_tol: float = 0.0):
         """One control step at states ``x`` [B, ns]: ``Plant.step``'s
         arguments and meaning.  Fills the device tensors Y, U, h, status, Fp,
         Mp, Fd, Md, Jp, Jd and returns self; one launch on torch's current
@@ -1390,7 +1421,7 @@ class SharedPlant(SharedProblem):
         B = int(x.shape[0]) if hasattr(x, "shape") and len(x.shape) == 2 else len(x)
         if B != self._Bstep or B != self.B:
             if B <= 0:
-                _check(lib().pqp_shared_step(self._h, B, *([None] * 3), 0, 1, *([None] * 10), None))
+                _check(lib().pqp_shared_step_tol(self._h, B, *([None] * 3), 0, 1, *([None] * 10), 0.0, 0.0, None))
             self.B = self._Bstep = B
             self.Y, self.U = torch.zeros(B, self.N, **f), torch.zeros(B, self.M, **f)
             self.h = torch.zeros(B, dtype=torch.int64, device=self.device)
@@ -1415,8 +1446,8 @@ class SharedPlant(SharedProblem):
         cap = self.max_updates if max_updates is None else int(max_updates)
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         self._inputs = (xt, Dt, Kt)  # alive until the next step: the launch is asynchronous
-        _check(lib().pqp_shared_step(self._h, B, p(xt), p(Dt), None if Kt is None else p(Kt), int(bool(warm)), cap,
-                                     *[p(getattr(self, k)) for k in self.OUT], stream))
+        _check(lib().pqp_shared_step_tol(self._h, B, p(xt), p(Dt), None if Kt is None else p(Kt), int(bool(warm)), cap,
+                                         *[p(getattr(self, k)) for k in self.OUT], float(abs_tol), float(rel_tol), stream))
         return self
 
 
