@@ -160,6 +160,12 @@ int pqp_tune(const char *key, long long value, long long *old_value);
  *                      out: workgroups of pqp_plant_step resident at once on the
  *                      current device (CUs x occupancy): its grid is min(B, that)
  *                      (the one-wave step's shapes, pqp_plant_kind 1)
+ *   plant_widths       in: *value = N | M << 8; out: NMAX | MMAX << 8, the widths of the
+ *                      k_plant_step instantiation that pqp_plant_step (either form of
+ *                      its iteration) and the fused pqp_plant_rollout run for a one-wave
+ *                      plant of (N, M), with or without tolerances: NMAX in 8, 16, 24,
+ *                      28, 32 and MMAX in 8, 16, 32, read off the launches' own dispatch.
+ *                      PQP_ERR_ARG where (N, M) is no one-wave plant's shape; host only
  *   plant_mid_lds      in: *value = N << 32 | M; out: bytes of LDS one workgroup of the
  *                      one-workgroup plant step (pqp.h 2g) takes; host only */
 int pqp_tune_get(const char *key, long long *value);

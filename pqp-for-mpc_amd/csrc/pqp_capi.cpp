@@ -3044,6 +3044,14 @@ extern "C" int pqp_tune_get(const char* key, long long* value) {
         *value = pqp::plant_resident_wgs(N, M, nd, ns, (v >> 32 & 1) != 0);
         return PQP_OK;
     }
+    if (std::strcmp(key, "plant_widths") == 0) {  // in: N | M << 8; out: NMAX | MMAX << 8 of k_plant_step's instantiation (host only)
+        const long long v = *value;
+        const int N = (int)(v & 255), M = (int)(v >> 8 & 255);
+        if ((v >> 16) != 0 || !pqp::plant_shape_ok(N, M, 1, 1))
+            return pqp::set_error(PQP_ERR_ARG, "pqp_tune_get: plant_widths of N=%d, M=%d: not a one-wave plant's shape", N, M);
+        *value = pqp::plant_widths(N, M);
+        return PQP_OK;
+    }
     if (std::strcmp(key, "plant_mid_lds") == 0) {  // in: N << 32 | M; out: bytes of LDS of the one-workgroup plant step (host only)
         const long long v = *value;
         const int N = (int)(v >> 32), M = (int)(v & 0xffffffff);

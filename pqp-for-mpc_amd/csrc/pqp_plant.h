@@ -42,6 +42,10 @@ extern int g_plant_pipe;
 bool plant_shape_ok(int N, int M, int nd, int ns);
 // bytes of LDS one workgroup (one wave) of the step takes
 size_t plant_lds_bytes(int N, int M, int nd, int ns);
+// NMAX | MMAX << 8 of the k_plant_step instantiation that the launches below pick for (N, M) -- the step in
+// both forms and the fused rollout, under either stopping rule; 0 if they would not all pick the same one.
+// Host only: it compares the dispatch's kernel pointers (tests: which cases reach which of the 15 widths).
+int plant_widths(int N, int M);
 // Workgroups of the form `pipe` resident on the current device at once (its
 // CUs times the occupancy of the shape's instantiation); 0 with the error left
 // in hipGetLastError.  Queried once per plant, never in a step.

@@ -254,7 +254,35 @@ RollKernel roll_kernel(int N, int M, bool tol = false) {  // plant_kernel's widt
     return roll_kernel_m<32>(M, tol);
 }
 
+// plant_widths: the dispatch above asked which instantiation it picks -- true where the plain step, the
+// pipelined step and the rollout of (N, M), under either rule, are all the <NMAX, MMAX> kernels
+template <int NMAX, int MMAX>
+bool plant_runs_at(int N, int M) {
+    for (int tol = 0; tol < 2; ++tol)
+        if (plant_kernel(N, M, false, tol) != plant_kernel_t<NMAX, MMAX, false>(tol) ||
+            plant_kernel(N, M, true, tol) != plant_kernel_t<NMAX, MMAX, true>(tol) ||
+            roll_kernel(N, M, tol) != roll_kernel_t<NMAX, MMAX>(tol))
+            return false;
+    return true;
+}
+template <int NMAX>
+int plant_widths_n(int N, int M) {
+    if (plant_runs_at<NMAX, 8>(N, M)) return NMAX | 8 << 8;
+    if (plant_runs_at<NMAX, 16>(N, M)) return NMAX | 16 << 8;
+    if (plant_runs_at<NMAX, 32>(N, M)) return NMAX | 32 << 8;
+    return 0;
+}
+
 }  // namespace
+
+int plant_widths(int N, int M) {
+    int w = plant_widths_n<8>(N, M);
+    if (!w) w = plant_widths_n<16>(N, M);
+    if (!w) w = plant_widths_n<24>(N, M);
+    if (!w) w = plant_widths_n<28>(N, M);
+    if (!w) w = plant_widths_n<32>(N, M);
+    return w;
+}
 
 int g_plant_roll_chain = 0;
 

@@ -18,7 +18,10 @@ pytestmark = pytest.mark.gpu
 
 CAP = 2000
 FIELDS = ("Y", "U", "h", "status", "Fp", "Mp", "Fd", "Md", "Jp", "Jd")
-# (N, M, nd, ns): every NMAX and MMAX instantiation, the N + M = 63 edge, odd ns and nd, both 64 limits
+# (N, M, nd, ns): every NMAX value and every MMAX value, but not every pair: of the 15 (NMAX, MMAX) instantiations
+# these are 8x8, 16x16, 24x8, 28x16 and 32x32 (twice), six with the bundled plant's 28x8; the N + M = 63 edge, odd ns
+# and nd, both 64 limits.  At test_shapes' cap of 12 every state ends capped, some without a feasible iterate: all
+# 15 pairs, on states that converge, are tests/test_gpu_plant_widths.py's
 SHAPES = [(8, 2, 1, 3), (16, 12, 3, 5), (24, 8, 2, 37), (28, 16, 1, 29), (32, 31, 4, 64), (31, 32, 64, 1)]
 
 

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from conftest import EXAMPLE_DIR, assert_bitwise
+from plant_widths_ref import seeded_dynamics  # noqa: F401  (tests/test_gpu_stop.py and tests/test_stop_ref.py take it from here)
 from rollout_ref import ref_advance_batch, ref_closed_loop
 from test_gpu_plant import synth_plant
 from warm_ref import CAPPED, DONE
@@ -53,15 +54,6 @@ def bits_or_nan(actual, expected, what):
     assert a.shape == e.shape, (what, a.shape, e.shape)
     assert np.array_equal(np.isnan(a), np.isnan(e)), f"{what}: NaN positions differ"
     assert_bitwise(np.where(np.isnan(e), np.float32(0), a).reshape(-1), np.where(np.isnan(e), np.float32(0), e).reshape(-1), what)
-
-
-def seeded_dynamics(ns, M, nd, seed, bu=1.0):
-    """A = 0.9 I + 0.01 U(-1, 1), Bu = bu U(-1, 1), Bd = 0.01 U(-1, 1), drawn in this order."""
-    rng = np.random.default_rng(seed)
-    A = (0.9 * np.eye(ns) + 0.01 * rng.uniform(-1, 1, (ns, ns))).astype(np.float32)
-    Bu = (bu * rng.uniform(-1, 1, (ns, M))).astype(np.float32)
-    Bd = (0.01 * rng.uniform(-1, 1, (ns, nd))).astype(np.float32)
-    return A, Bu, Bd
 
 
 def by_hand(gpu_lib, pl, dyn, x0, K, D=None, Kp=None, Y0=None, floor=None, cap=None) -> dict:
