@@ -166,6 +166,13 @@ int pqp_tune(const char *key, long long value, long long *old_value);
  *                      plant of (N, M), with or without tolerances: NMAX in 8, 16, 24,
  *                      28, 32 and MMAX in 8, 16, 32, read off the launches' own dispatch.
  *                      PQP_ERR_ARG where (N, M) is no one-wave plant's shape; host only
+ *   plant_mid_build    in: *value = N; out: threads | pair << 16 | lean << 17 | band << 18, the
+ *                      build of the one-workgroup plant step (pqp.h 2g) that pqp_plant_step
+ *                      runs for a plant of N rows, with or without tolerances: the
+ *                      workgroup's threads, and whether the build has lane sides
+ *                      (96 <= N <= 128), the lean rings (N <= 95) and the band table
+ *                      (N > 64), read off the launch's own dispatch.  PQP_ERR_ARG
+ *                      where N is not in 1..192; host only
  *   plant_mid_lds      in: *value = N << 32 | M; out: bytes of LDS one workgroup of the
  *                      one-workgroup plant step (pqp.h 2g) takes; host only */
 int pqp_tune_get(const char *key, long long *value);

@@ -3052,6 +3052,13 @@ extern "C" int pqp_tune_get(const char* key, long long* value) {
         *value = pqp::plant_widths(N, M);
         return PQP_OK;
     }
+    if (std::strcmp(key, "plant_mid_build") == 0) {  // in: N; out: threads | pair << 16 | lean << 17 | band << 18 of k_plant_step_mid's build (host only)
+        const long long v = *value;
+        if (v < 1 || v > 192)  // plant_mid_shape_ok's range of N (M decides the rest, not the build)
+            return pqp::set_error(PQP_ERR_ARG, "pqp_tune_get: plant_mid_build of N=%lld: not a one-workgroup plant's N", v);
+        *value = pqp::plant_mid_build((int)v);
+        return PQP_OK;
+    }
     if (std::strcmp(key, "plant_mid_lds") == 0) {  // in: N << 32 | M; out: bytes of LDS of the one-workgroup plant step (host only)
         const long long v = *value;
         const int N = (int)(v >> 32), M = (int)(v & 0xffffffff);

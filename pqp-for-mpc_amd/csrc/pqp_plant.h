@@ -115,6 +115,11 @@ struct PlantMidFlags {
 bool plant_mid_shape_ok(int N, int M, int nd, int ns);
 // bytes of LDS one workgroup of the step takes (mid2_layout and the prologue's words)
 size_t plant_mid_lds_bytes(int N, int M);
+// threads | pair << 16 | lean << 17 | band << 18 of the k_plant_step_mid build that the launch below picks for N,
+// under either stopping rule: the workgroup's threads, lane sides (<1024, true>), the lean rings (<384, false, 6>),
+// the band table (every build but N <= 64's); 0 if the two rules would not pick the same build.  Host only: it
+// compares the dispatch's kernel pointers (tests: which cases reach which of the four builds).
+int plant_mid_build(int N);
 // Workgroups resident on the current device at once; 0 with the error left in
 // hipGetLastError.  Queried once per plant, never in a step.
 int plant_mid_resident_wgs(int N, int M);

@@ -104,7 +104,25 @@ PlantMidKernel plant_mid_kernel(int N, bool tol = false) {
     return tol ? k_plant_step_mid_tol<1024, false> : k_plant_step_mid<1024, false>;
 }
 
+// plant_mid_build: the dispatch above asked which build it picks -- true where both kernels of (N), with and
+// without the tolerances, are the <MAXT, PAIR, MINW, BAND> ones
+template <int MAXT, bool PAIR, int MINW = 1, bool BAND = true>
+bool plant_mid_runs_at(int N) {
+    return plant_mid_kernel(N, false) == k_plant_step_mid<MAXT, PAIR, MINW, BAND> &&
+           plant_mid_kernel(N, true) == k_plant_step_mid_tol<MAXT, PAIR, MINW, BAND>;
+}
+
 }  // namespace
+
+int plant_mid_build(int N) {
+    const int threads = plant_mid_threads(N);
+    const int pair = 1 << 16, lean = 1 << 17, band = 1 << 18;
+    if (plant_mid_runs_at<384, false, 6, false>(N)) return threads | lean;
+    if (plant_mid_runs_at<384, false, 6>(N)) return threads | lean | band;
+    if (plant_mid_runs_at<1024, true>(N)) return threads | pair | band;
+    if (plant_mid_runs_at<1024, false>(N)) return threads | band;
+    return 0;
+}
 
 size_t plant_mid_lds_bytes(int N, int M) {
     return sizeof(float) * ((size_t)plant_mid_front(N) + (size_t)mid2_layout(N, M, true).total);

@@ -67,7 +67,10 @@ def test_shapes(gpu_lib, orc, shape):
 
 
 def test_qd_not_bit_symmetric(gpu_lib, orc):
-    """A dense Qp_inv: convertToDual's Qd is not bit-symmetric, so Y'Qd walks columns."""
+    """A dense Qp_inv: convertToDual's Qd is not bit-symmetric, and create finds that (sym == false) while
+    the setup, the prologue and the update stay the oracle's.  At cap 12 every state ends capped before an
+    iterate passes checkFeas, so the column walk of Y'Qd, which reaches an output through Jd alone, is not
+    in what this test compares: tests/test_gpu_plant_mid_builds.py's dense cases observe it."""
     shape = (56, 14, 1, 29)
     N, M, nd, ns = shape
     A, states = synth_plant(orc, N, M, nd, ns, 5)
