@@ -726,7 +726,8 @@ int pqp_shared_step(pqp_shared *p, int B, const float *d_x, const float *d_D, co
  * one-workgroup plants of 2g (and for 2f's under the tuning key
  * plant_roll_chain = 1) as a chain of 2 K launches, k_plant_step or
  * k_plant_step_mid then k_plant_advance, K times (one more launch, the floor,
- * when warm != 0 and y_floor > 0), with no host work in between.
+ * when warm != 0 and y_floor > 0), with no host work in between.  (2l: the
+ * one-workgroup plants' own one-launch form, and the caller's choice of form.)
  *
  * The state update is the reference's own primitives, three matrixMultiply
  * (PQP_CPU.c:84) and two matrixAdd (:157): t = A x, v = Bu U, w = Bd D, every
@@ -843,6 +844,43 @@ int pqp_shared_step_tol(pqp_shared *p, int B, const float *d_x, const float *d_D
                         long long max_updates, float *d_Y, float *d_U, long long *d_h, int *d_status,
                         float *d_Fp, float *d_Mp, float *d_Fd, float *d_Md, float *d_Jp, float *d_Jd,
                         float abs_tol, float rel_tol, void *stream);
+
+/* ----------------------------------------------------------------------
+ * 2l. The rollout's form, chosen by the caller.
+ * pqp_plant_rollout (2j) and pqp_plant_rollout_tol (2k) pick the form of the
+ * closed loop themselves: ONE launch for the one-wave plants of 2f, the chain
+ * of 2 K launches for the one-workgroup plants of 2g.  The one-workgroup plants
+ * have a fused form too (k_plant_roll_mid: k_plant_step_mid with a step loop
+ * inside its state loop).  A workgroup stages the plant once and carries its
+ * state through all K steps: step k's Y goes to d_Y[b] and is read back,
+ * floored, for step k + 1 after a barrier, and one wave forms X[k + 1][b] with
+ * 2j's arithmetic from the dynamics' device copies.  The launch takes the
+ * step's LDS, so every shape of 2g has it.  pqp_plant_rollout_form is
+ * pqp_plant_rollout_tol with that choice as an argument; the defaults of 2j
+ * and 2k, pqp_plant_rollout_fused's answers and the tuning keys keep their
+ * meaning.
+ *
+ * The contract is pqp_plant_rollout_tol's, word for word, in every form:
+ * asynchronous on `stream`, no allocation, no synchronisation, no copy to the
+ * host, the caller's device restored, capturable in a graph, and the same bits
+ * in all seven outputs (X, Y, U, h, status, Jp, Jd) whatever the form.  Every
+ * argument error is PQP_ERR_ARG before any device is looked for: the tolerances
+ * first (2k), then a `form` outside 0..2, then 2j's.  PQP_ROLL_FUSED on a plant
+ * made on a device where the fused launch has no occupancy is PQP_ERR_ARG too.
+ * -------------------------------------------------------------------- */
+#define PQP_ROLL_DEFAULT 0 /* what pqp_plant_rollout_tol does (fused for kind 1, the chain for kind 2; tuning keys honoured) */
+#define PQP_ROLL_CHAIN 1   /* the chain of step and advance launches, either kind */
+#define PQP_ROLL_FUSED 2   /* ONE launch, either kind */
+
+/* Bit (1 << form) set for each of PQP_ROLL_CHAIN, PQP_ROLL_FUSED that a plant of that shape can run
+ * (6 for every shape of 2f and 2g today); 0: no plant's shape.  No device needed, no error set. */
+int pqp_plant_rollout_forms(int N, int M, int nd, int ns);
+
+/* pqp_plant_rollout_tol's arguments, then `form` before `stream`. */
+int pqp_plant_rollout_form(pqp_plant *p, const pqp_dynamics *dyn, int B, int K, float *d_X, const float *d_D,
+                           int D_steps, const float *d_Kp, int warm, float y_floor, long long max_updates,
+                           float *d_Y, float *d_U, long long *d_h, int *d_status, float *d_Jp, float *d_Jd,
+                           float abs_tol, float rel_tol, int form, void *stream);
 
 #ifdef __cplusplus
 }

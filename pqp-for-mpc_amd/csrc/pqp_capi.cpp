@@ -427,6 +427,7 @@ struct pqp_plant {
     pqp::DevBuf Fp1, Fp2, Fp3, Mp1, Mp2, Mp3, Mp4, Mp5, Mp6;
     pqp::PlantData data{};
     int roll_slots = 0;      // kind 1: workgroups of the fused rollout resident at once (0: the rollout is the chain)
+    int roll_mid_slots = 0;  // kind 2: workgroups of k_plant_roll_mid resident at once (0: PQP_ROLL_FUSED is refused)
 };
 
 // A plant's state update x+ = (A x + Bu U) + Bd D resident on its device (pqp_dynamics_*, 2j): the three
@@ -2098,6 +2099,13 @@ static int plant_create(const char* fn, bool horizon, int device, int N, int M, 
             P->roll_slots = 0;
         }
     }
+    if (kind == 2) {  // 2l: the fused rollout's grid bound; a plant that steps is made as before
+        P->roll_mid_slots = plant_mid_roll_resident_wgs(N, M);
+        if (P->roll_mid_slots <= 0) {
+            (void)hipGetLastError();
+            P->roll_mid_slots = 0;
+        }
+    }
     if (kind == 2) {
         // what k_solve_mid2 finds in Qd when it stages a problem, once: bit symmetry by the batched
         // entry points' kernel, NaN / inf by a scan of the host copy
@@ -2295,12 +2303,22 @@ int pqp_dynamics_advance(const pqp_dynamics* d, int B, const float* d_x, const f
 
 int pqp_plant_rollout_fused(int N, int M, int nd, int ns) { return plant_roll_shape_ok(N, M, nd, ns) ? 1 : 0; }
 
-// pqp_plant_rollout (tolerances 0, 0) and pqp_plant_rollout_tol
+int pqp_plant_rollout_forms(int N, int M, int nd, int ns) {
+    const int chain = 1 << PQP_ROLL_CHAIN, fused = 1 << PQP_ROLL_FUSED;
+    if (plant_shape_ok(N, M, nd, ns)) return chain | (plant_roll_shape_ok(N, M, nd, ns) ? fused : 0);
+    if (plant_mid_shape_ok(N, M, nd, ns)) return chain | fused;  // k_plant_roll_mid takes the step's LDS
+    return 0;
+}
+
+// pqp_plant_rollout (tolerances 0, 0), pqp_plant_rollout_tol (both PQP_ROLL_DEFAULT) and pqp_plant_rollout_form
 static int plant_rollout(const char* fn, pqp_plant* p, const pqp_dynamics* dyn, int B, int K, float* d_X,
                          const float* d_D, int D_steps, const float* d_Kp, int warm, float y_floor,
                          long long max_updates, float* d_Y, float* d_U, long long* d_h, int* d_status, float* d_Jp,
-                         float* d_Jd, float abs_tol, float rel_tol, void* stream) {
+                         float* d_Jd, float abs_tol, float rel_tol, int form, void* stream) {
     PQP_TRY(check_tols(fn, abs_tol, rel_tol));
+    if (form < PQP_ROLL_DEFAULT || form > PQP_ROLL_FUSED)
+        return set_error(PQP_ERR_ARG, "%s: form = %d is none of PQP_ROLL_DEFAULT, PQP_ROLL_CHAIN, PQP_ROLL_FUSED", fn,
+                         form);
     if (!p) return set_error(PQP_ERR_ARG, "%s: null plant", fn);
     if (!dyn) return set_error(PQP_ERR_ARG, "%s: null dynamics", fn);
     if (B <= 0) return set_error(PQP_ERR_ARG, "%s: B = %d states", fn, B);
@@ -2326,13 +2344,27 @@ static int plant_rollout(const char* fn, pqp_plant* p, const pqp_dynamics* dyn, 
     S.Kp = d_Kp;
     S.Y = d_Y;
     S.abs_tol = abs_tol, S.rel_tol = rel_tol;
+    const int fused_slots = p->kind == 1 ? p->roll_slots : p->roll_mid_slots;
+    if (form == PQP_ROLL_FUSED && fused_slots <= 0)
+        return set_error(PQP_ERR_ARG, "%s: PQP_ROLL_FUSED, but the fused launch of this plant (N=%d, M=%d, nd=%d, ns=%d) "
+                                      "has no occupancy on device %d: use PQP_ROLL_CHAIN", fn, p->N, p->M, p->nd, p->ns,
+                         p->dev);
+    // the default: one launch for kind 1 (unless plant_roll_chain says otherwise), the chain for kind 2
+    const bool fused = form == PQP_ROLL_FUSED ||
+                       (form == PQP_ROLL_DEFAULT && p->kind == 1 && p->roll_slots > 0 && !g_plant_roll_chain);
     DeviceGuard on(p->dev);
-    if (p->kind == 1 && p->roll_slots > 0 && !g_plant_roll_chain) {  // ONE launch: k_plant_step's ROLL form
+    if (fused) {  // ONE launch: the ROLL form of k_plant_step (kind 1) or of k_plant_step_mid (kind 2, 2l)
         S.warm = warm ? 1 : 0;
         S.D = d_D;
         S.U = d_U, S.h = d_h, S.status = d_status, S.Jp = d_Jp, S.Jd = d_Jd;
         const PlantRoll R{K, D_steps, y_floor, d_X, dyn->data};
-        PQP_HIP(launch_plant_roll(p->data, S, R, p->roll_slots, s));
+        if (p->kind == 2) {
+            PlantMidFlags F = p->mid;
+            F.dense = g_tune.mid2_dense ? 1 : 0;
+            PQP_HIP(launch_plant_roll_mid(p->data, S, F, R, p->roll_mid_slots, s));
+        } else {
+            PQP_HIP(launch_plant_roll(p->data, S, R, p->roll_slots, s));
+        }
         return PQP_OK;
     }
     // the chain: K times the step and the advance, which also floors Y for the next step
@@ -2360,7 +2392,7 @@ int pqp_plant_rollout(pqp_plant* p, const pqp_dynamics* dyn, int B, int K, float
                       const float* d_Kp, int warm, float y_floor, long long max_updates, float* d_Y, float* d_U,
                       long long* d_h, int* d_status, float* d_Jp, float* d_Jd, void* stream) {
     return plant_rollout("pqp_plant_rollout", p, dyn, B, K, d_X, d_D, D_steps, d_Kp, warm, y_floor, max_updates, d_Y,
-                         d_U, d_h, d_status, d_Jp, d_Jd, 0.0f, 0.0f, stream);
+                         d_U, d_h, d_status, d_Jp, d_Jd, 0.0f, 0.0f, PQP_ROLL_DEFAULT, stream);
 }
 
 int pqp_plant_rollout_tol(pqp_plant* p, const pqp_dynamics* dyn, int B, int K, float* d_X, const float* d_D,
@@ -2368,7 +2400,15 @@ int pqp_plant_rollout_tol(pqp_plant* p, const pqp_dynamics* dyn, int B, int K, f
                           float* d_U, long long* d_h, int* d_status, float* d_Jp, float* d_Jd, float abs_tol,
                           float rel_tol, void* stream) {
     return plant_rollout("pqp_plant_rollout_tol", p, dyn, B, K, d_X, d_D, D_steps, d_Kp, warm, y_floor, max_updates,
-                         d_Y, d_U, d_h, d_status, d_Jp, d_Jd, abs_tol, rel_tol, stream);
+                         d_Y, d_U, d_h, d_status, d_Jp, d_Jd, abs_tol, rel_tol, PQP_ROLL_DEFAULT, stream);
+}
+
+int pqp_plant_rollout_form(pqp_plant* p, const pqp_dynamics* dyn, int B, int K, float* d_X, const float* d_D,
+                           int D_steps, const float* d_Kp, int warm, float y_floor, long long max_updates, float* d_Y,
+                           float* d_U, long long* d_h, int* d_status, float* d_Jp, float* d_Jd, float abs_tol,
+                           float rel_tol, int form, void* stream) {
+    return plant_rollout("pqp_plant_rollout_form", p, dyn, B, K, d_X, d_D, D_steps, d_Kp, warm, y_floor, max_updates,
+                         d_Y, d_U, d_h, d_status, d_Jp, d_Jd, abs_tol, rel_tol, form, stream);
 }
 
 // ---------------------------------------------------------------------------

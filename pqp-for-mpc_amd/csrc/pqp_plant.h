@@ -127,4 +127,13 @@ int plant_mid_resident_wgs(int N, int M);
 hipError_t launch_plant_step_mid(const PlantData& P, const PlantStep& S, const PlantMidFlags& F, int slots,
                                  hipStream_t s);
 
+// ---- the one-workgroup plants' fused rollout (pqp_plant_mid.hip, pqp.h 2l): k_plant_step_mid's ROLL form ----
+// Every shape of plant_mid_shape_ok has it: the launch takes the step's LDS (the dynamics are read through L2).
+// Workgroups resident on the current device at once; 0 with the error left in hipGetLastError.
+int plant_mid_roll_resident_wgs(int N, int M);
+// ONE launch of K steps: state b's trajectory on workgroup b mod grid; no allocation, no synchronisation.
+// S and R as launch_plant_roll's; slots: plant_mid_roll_resident_wgs' count.
+hipError_t launch_plant_roll_mid(const PlantData& P, const PlantStep& S, const PlantMidFlags& F, const PlantRoll& R,
+                                 int slots, hipStream_t s);
+
 }  // namespace pqp

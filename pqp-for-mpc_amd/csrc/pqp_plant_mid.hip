@@ -75,8 +75,48 @@ __device__ __forceinline__ PlantMidArgsPtr plant_mid_args() {
     return a;
 }
 
+// The fused rollout's argument (pqp.h 2l): the step's three, each at the offset it has in PlantMidArgs (so
+// plant_mid_args() reads them in either kernel), then the rollout's, read through a pointer as opaque.  S's
+// arrays then carry a leading K axis (U, h, status, Jp, Jd), its D is [d_steps][B][nd] and its x is unused.
+struct PlantMidRollArgs {
+    PlantData P;
+    PlantStep S;
+    PlantMidFlags F;
+    PlantRoll R;
+};
+static_assert(offsetof(PlantMidRollArgs, P) == offsetof(PlantMidArgs, P) &&
+                  offsetof(PlantMidRollArgs, S) == offsetof(PlantMidArgs, S) &&
+                  offsetof(PlantMidRollArgs, F) == offsetof(PlantMidArgs, F),
+              "the step's words keep their offsets");
+typedef const __attribute__((address_space(4))) PlantMidRollArgs* PlantMidRollArgsPtr;
+__device__ __forceinline__ PlantMidRollArgsPtr plant_mid_roll_args() {
+    PlantMidRollArgsPtr a = (PlantMidRollArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(a));
+    return a;
+}
+
+// The rollout's state update, one matrixMultiply (PQP_CPU.c:84) on one wave: sum over j < n of Mt[j * ld + r] * v_j
+// for this lane's row r, in index order from +0.0f, every product rounded before its add.  Mt is k-major in memory
+// (the lanes' words of one j consecutive) and v_j is lane j's `vl` (n <= 64).  Eight rows are loaded ahead of their
+// adds, so a step pays an eighth of the sum's memory latencies; a row past n - 1 is loaded as row n - 1 and not added.
+// Every lane of the wave calls it.
+__device__ __forceinline__ float plant_mid_dot_lanes(const float* Mt, int ld, int r, int n, float vl) {
+    float s = 0.0f;
+    for (int j = 0; j < n; j += 8) {
+        float a[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) a[u] = Mt[(j + u < n ? j + u : n - 1) * ld + r];
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            if (j + u < n) s += a[u] * __shfl(vl, j + u);
+    }
+    return s;
+}
+
 // k_plant_step_mid and k_plant_step_mid_tol: one text (pqp_plant_mid_step.inc), compiled with and without
-// the caller's gap tolerances (pqp.h 2k)
+// the caller's gap tolerances (pqp.h 2k); k_plant_roll_mid and k_plant_roll_mid_tol: the same
+// text with the step loop of the fused rollout (pqp.h 2l)
+#define PQP_PLANT_MID_ROLL false
 #define PQP_PLANT_MID_KERNEL k_plant_step_mid
 #define PQP_PLANT_MID_TOL false
 #include "pqp_plant_mid_step.inc"
@@ -87,8 +127,22 @@ __device__ __forceinline__ PlantMidArgsPtr plant_mid_args() {
 #include "pqp_plant_mid_step.inc"
 #undef PQP_PLANT_MID_KERNEL
 #undef PQP_PLANT_MID_TOL
+#undef PQP_PLANT_MID_ROLL
+#define PQP_PLANT_MID_ROLL true
+#define PQP_PLANT_MID_KERNEL k_plant_roll_mid
+#define PQP_PLANT_MID_TOL false
+#include "pqp_plant_mid_step.inc"
+#undef PQP_PLANT_MID_KERNEL
+#undef PQP_PLANT_MID_TOL
+#define PQP_PLANT_MID_KERNEL k_plant_roll_mid_tol
+#define PQP_PLANT_MID_TOL true
+#include "pqp_plant_mid_step.inc"
+#undef PQP_PLANT_MID_KERNEL
+#undef PQP_PLANT_MID_TOL
+#undef PQP_PLANT_MID_ROLL
 
 typedef void (*PlantMidKernel)(PlantMidArgs);
+typedef void (*PlantMidRollKernel)(PlantMidRollArgs);
 
 // launch_mid_grid's choice of k_solve_mid2's build at its default knobs
 inline bool plant_mid_pair(int N) { return N >= 96 && N <= 128; }
@@ -102,6 +156,16 @@ PlantMidKernel plant_mid_kernel(int N, bool tol = false) {
     if (lean) return tol ? k_plant_step_mid_tol<384, false, 6, false> : k_plant_step_mid<384, false, 6, false>;
     if (pair) return tol ? k_plant_step_mid_tol<1024, true> : k_plant_step_mid<1024, true>;
     return tol ? k_plant_step_mid_tol<1024, false> : k_plant_step_mid<1024, false>;
+}
+
+// the rollout's kernel: plant_mid_kernel's dispatch by N, build for build
+PlantMidRollKernel plant_mid_roll_kernel(int N, bool tol = false) {
+    const bool pair = plant_mid_pair(N);
+    const bool lean = plant_mid_threads(N) <= 384;
+    if (lean && N > 64) return tol ? k_plant_roll_mid_tol<384, false, 6> : k_plant_roll_mid<384, false, 6>;
+    if (lean) return tol ? k_plant_roll_mid_tol<384, false, 6, false> : k_plant_roll_mid<384, false, 6, false>;
+    if (pair) return tol ? k_plant_roll_mid_tol<1024, true> : k_plant_roll_mid<1024, true>;
+    return tol ? k_plant_roll_mid_tol<1024, false> : k_plant_roll_mid<1024, false>;
 }
 
 // plant_mid_build: the dispatch above asked which build it picks -- true where both kernels of (N), with and
@@ -146,6 +210,27 @@ int plant_mid_resident_wgs(int N, int M) {
                                                      plant_mid_lds_bytes(N, M)) != hipSuccess)
         return 0;
     return cus * per_cu;
+}
+
+int plant_mid_roll_resident_wgs(int N, int M) {
+    int dev = 0, cus = 0, per_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, plant_mid_roll_kernel(N), plant_mid_threads(N),
+                                                     plant_mid_lds_bytes(N, M)) != hipSuccess)
+        return 0;
+    return cus * per_cu;
+}
+
+hipError_t launch_plant_roll_mid(const PlantData& P, const PlantStep& S, const PlantMidFlags& F, const PlantRoll& R,
+                                 int slots, hipStream_t s) {
+    int grid = S.B < slots ? S.B : slots;
+    if (g_plant_grid > 0 && grid > g_plant_grid) grid = g_plant_grid;
+    if (grid < 1) grid = 1;
+    const PlantMidRollArgs A{P, S, F, R};
+    hipLaunchKernelGGL(plant_mid_roll_kernel(P.N, plant_step_tol(S)), dim3(grid), dim3(plant_mid_threads(P.N)),
+                       plant_mid_lds_bytes(P.N, P.M), s, A);
+    return hipGetLastError();
 }
 
 hipError_t launch_plant_step_mid(const PlantData& P, const PlantStep& S, const PlantMidFlags& F, int slots,

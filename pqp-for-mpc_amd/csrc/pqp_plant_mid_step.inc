@@ -4,8 +4,19 @@
 // Two kernels of one text, as pqp_plant_step.inc: with the flag compiled out, k_plant_step_mid's four builds
 // keep the instructions they had before the tolerances existed (DESIGN.md 4k).
 //
+// and twice more with PQP_PLANT_MID_ROLL true (false above), the fused rollout of pqp.h 2l:
+//   PQP_PLANT_MID_KERNEL k_plant_roll_mid,     PQP_PLANT_MID_TOL false
+//   PQP_PLANT_MID_KERNEL k_plant_roll_mid_tol, PQP_PLANT_MID_TOL true
+// ROLL (the argument is then a PlantMidRollArgs): a step loop inside the state loop.  The workgroup carries
+// state b through R.K steps on the plant it staged once: step k's prologue reads row k of X and this step's D,
+// every start but a cold step 0 is d_Y[b] (floored on load), the results go to row k of the [K][B] arrays and Y
+// to d_Y[b], and one wave forms x+ = (A x + Bu U) + Bd D into row k + 1 of X (k_plant_advance's arithmetic, the
+// dynamics read through L2) before the barrier that ends the step.  Every ROLL branch is a compile-time one and
+// the step loop a do ... while (ROLL && ...), so the step's eight kernels keep their instructions (DESIGN.md 4l).
+//
 template <int MAXT, bool PAIR, int MINW = 1, bool BAND = true>
-__global__ void __launch_bounds__(MAXT, MINW) PQP_PLANT_MID_KERNEL(PlantMidArgs A0) {
+__global__ void __launch_bounds__(MAXT, MINW)
+PQP_PLANT_MID_KERNEL(std::conditional_t<PQP_PLANT_MID_ROLL, PlantMidRollArgs, PlantMidArgs> A0) {
     extern __shared__ __attribute__((aligned(16))) float lds_raw[];
     if ((int)blockIdx.x >= A0.S.B) return;  // a workgroup without a state (uniform)
     const PlantData& P = A0.P;
@@ -126,13 +137,24 @@ __global__ void __launch_bounds__(MAXT, MINW) PQP_PLANT_MID_KERNEL(PlantMidArgs 
     const int nB = A0.S.B;
 
     for (int b = blockIdx.x; b < nB; b += gridDim.x) {
+        // ROLL: the step of state b's trajectory.  Through the phase loop it lies in sums[3], the one word of
+        // `sums` that the solve leaves alone, not in a register: the results read it back
+        int k = 0;
+        do {  // ROLL: state b's K steps; else once (the body keeps the state loop's indentation)
         // ================= the state's prologue =================
         const PlantMidArgsPtr ap = plant_mid_args();
         const auto& P = ap->P;  // (shadow the kernel's: see plant_mid_args)
         const auto& S = ap->S;
         const long long max_updates = S.max_updates;
-        if (tid < ns) xs[tid] = S.x[(size_t)b * ns + tid];
-        if (hw == 1 && lane < nd) ds[lane] = S.D[(size_t)b * nd + lane];
+        if constexpr (PQP_PLANT_MID_ROLL) {  // x: row k of X; D: this step's
+            const PlantMidRollArgsPtr ar = plant_mid_roll_args();
+            const size_t kb = (size_t)k * ar->S.B + b;
+            if (tid < ns) xs[tid] = ar->R.X[kb * ns + tid];
+            if (hw == 1 && lane < nd) ds[lane] = S.D[(ar->R.d_steps > 1 ? kb : (size_t)b) * nd + lane];
+        } else {
+            if (tid < ns) xs[tid] = S.x[(size_t)b * ns + tid];
+            if (hw == 1 && lane < nd) ds[lane] = S.D[(size_t)b * nd + lane];
+        }
         __syncthreads();
         // computeFp (:373) on wave 0; x'Mp1, D'Mp2 on wave 1, D'Mp3 on wave 2: one lane per column
         if (hw == 0) {
@@ -214,6 +236,8 @@ __global__ void __launch_bounds__(MAXT, MINW) PQP_PLANT_MID_KERNEL(PlantMidArgs 
         if (tid < 4) {
             fdy[tid] = 0.0f;
             sums[tid] = 0.0f;
+            // (the four lanes store one value, after lane 3's zero: no lane mask of its own to keep)
+            if constexpr (PQP_PLANT_MID_ROLL) reinterpret_cast<int*>(sums)[3] = k;
         }
         __syncthreads();
         // Mp's halved terms in k_mp_finish's order, Md = (Fp'Qp_inv) Fp - Mp (:475-478)
@@ -231,10 +255,22 @@ __global__ void __launch_bounds__(MAXT, MINW) PQP_PLANT_MID_KERNEL(PlantMidArgs 
         }
         __syncthreads();  // the prologue's words are dead: the rings, zero but for Y_1
         int ynf = 0;
+        // ROLL: every step but a cold step 0 starts from d_Y[b], which the step before stored (a barrier since:
+        // one workgroup reads its own global stores), floored on load as k_plant_advance / k_plant_floor floor it
+        bool warm_k = false;
+        float yfl = 0.0f;
+        if constexpr (PQP_PLANT_MID_ROLL) {
+            warm_k = k > 0 || S.warm;
+            yfl = plant_mid_roll_args()->R.y_floor;
+        }
         for (int e = tid; e < 5 * nk; e += NT) {
             const int i = e - (h0 % 3) * nk;
             float y = 0.0f;
             if (i >= 0 && i < N) {
+                if constexpr (PQP_PLANT_MID_ROLL) {
+                    y = warm_k ? S.Y[(size_t)b * N + i] : 1000.0f;
+                    if (warm_k && yfl > 0.0f) y = yfl > y ? yfl : y;  // (a NaN stays)
+                } else
                 y = S.warm ? S.Y[(size_t)b * N + i] : 1000.0f;  // initMat(Y,1000) :710
                 if (!(PQP_M2_PF ? (y >= 0.0f && y <= 3.402823466e38f) : fabsf(y) <= 3.402823466e38f)) ynf = 1;
             }
@@ -415,6 +451,41 @@ __global__ void __launch_bounds__(MAXT, MINW) PQP_PLANT_MID_KERNEL(PlantMidArgs 
             const auto& S = ao->S;
             const float* yo = Yr + (t_out % 3) * nk;
             for (int i = tid; i < N; i += NT) S.Y[(size_t)b * N + i] = yo[i];
+            if constexpr (PQP_PLANT_MID_ROLL) {
+                // ---- the step's results in row k of the [K][B] arrays; then x+ into row k + 1 of X ----
+                k = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(sums)[3]);
+                const size_t kb = (size_t)k * S.B + b;
+                for (int i = tid; i < M; i += NT) S.U[kb * M + i] = Us[(t_out & 1) * mk + i];
+                if (DEC1 ? (wave == wDec && lane == 0) : tid == 0) {
+                    if (S.h) S.h[kb] = t_out;
+                    if (S.status) S.status[kb] = status;
+                    if (S.Jp) S.Jp[kb] = costs ? Jp_last : __builtin_nanf("");
+                    if (S.Jd) S.Jd[kb] = costs ? Jd_last : __builtin_nanf("");
+                }
+                // x+ = (A x + 1 Bu U) + 1 Bd D on the first wave, k_plant_advance's sums: one lane per row, every
+                // sum from +0.0f in index order, every product rounded before its add.  x (row k of X: the LDS copy
+                // is dead), D and U (the ring slot stored above) one word per lane, handed round the wave; AT, BuT,
+                // BdT k-major from memory, consecutive over the lanes, eight rows loaded ahead of their adds.  The
+                // thread number and the sizes come from opaque copies, as k_plant_step's ROLL form takes them: no
+                // lane mask or per-lane address of this block is formed before the phase loop and held through it
+                int t2 = tid;
+                asm volatile("" : "+v"(t2));
+                if (t2 < 64) {
+                    const PlantMidRollArgsPtr ar = plant_mid_roll_args();
+                    const auto& R = ar->R;
+                    const int ns2 = ar->P.ns, nd2 = ar->P.nd, M2 = ar->P.M;
+                    const float xl = t2 < ns2 ? R.X[kb * ns2 + t2] : 0.0f;
+                    const float dl = t2 < nd2 ? S.D[(R.d_steps > 1 ? kb : (size_t)b) * nd2 + t2] : 0.0f;
+                    const float ul = t2 < M2 ? Us[(t_out & 1) * mk + t2] : 0.0f;
+                    const int pr = t2 < ns2 ? t2 : 0;
+                    const float t = plant_mid_dot_lanes(R.dyn.AT, ns2, pr, ns2, xl);
+                    const float v = plant_mid_dot_lanes(R.dyn.BuT, ns2, pr, M2, ul);
+                    const float w = plant_mid_dot_lanes(R.dyn.BdT, ns2, pr, nd2, dl);
+                    float xn = t + 1.0f * v;
+                    xn = xn + 1.0f * w;
+                    if (t2 < ns2) R.X[(kb + S.B) * ns2 + t2] = xn;
+                }
+            } else {
             for (int i = tid; i < M; i += NT) S.U[(size_t)b * M + i] = Us[(t_out & 1) * mk + i];
             if (DEC1 ? (wave == wDec && lane == 0) : tid == 0) {  // a thread that took the decisions
                 if (S.h) S.h[b] = t_out;
@@ -422,7 +493,9 @@ __global__ void __launch_bounds__(MAXT, MINW) PQP_PLANT_MID_KERNEL(PlantMidArgs 
                 if (S.Jp) S.Jp[b] = costs ? Jp_last : __builtin_nanf("");
                 if (S.Jd) S.Jd[b] = costs ? Jd_last : __builtin_nanf("");
             }
+            }
         }
-        __syncthreads();  // the next state's stores come after this one's reads
+        __syncthreads();  // the next state's (ROLL: step's) stores and loads come after this one's reads and stores
+        } while (PQP_PLANT_MID_ROLL && ++k < plant_mid_roll_args()->R.K);
     }
 }

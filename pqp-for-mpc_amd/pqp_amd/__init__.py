@@ -136,6 +136,9 @@ SIGNATURES = {
                            + [C.c_float, C.c_float, _vp]),
     "pqp_plant_rollout_tol": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.c_float,
                                         C.c_longlong] + [_vp] * 6 + [C.c_float, C.c_float, _vp]),
+    "pqp_plant_rollout_forms": (C.c_int, [C.c_int] * 4),
+    "pqp_plant_rollout_form": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, C.c_float,
+                                         C.c_longlong] + [_vp] * 6 + [C.c_float, C.c_float, C.c_int, _vp]),
     "pqp_shared_solve_tol": (C.c_int, [_vp, C.c_int] + [_vp] * 5 + [C.c_longlong] + [_vp] * 7
                              + [C.c_float, C.c_float, _vp]),
     "pqp_shared_step_tol": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_longlong] + [_vp] * 10
@@ -1098,9 +1101,18 @@ class Plant:
         """True where ``rollout`` of that shape is one launch (pqp_plant_rollout_fused)."""
         return bool(lib().pqp_plant_rollout_fused(int(N), int(M), int(nd), int(ns)))
 
+    ROLL_FORMS = {"default": 0, "chain": 1, "fused": 2}  # PQP_ROLL_DEFAULT, PQP_ROLL_CHAIN, PQP_ROLL_FUSED
+
+    @staticmethod
+    def rollout_forms(N: int, M: int, nd: int, ns: int) -> tuple:
+        """The forms ``rollout(form=...)`` of a plant of that shape can run, of "chain" and "fused"
+        (pqp_plant_rollout_forms); empty where the shape is no plant's."""
+        bits = lib().pqp_plant_rollout_forms(int(N), int(M), int(nd), int(ns))
+        return tuple(n for n in ("chain", "fused") if bits >> Plant.ROLL_FORMS[n] & 1)
+
     def rollout(self, x0, K: int, dynamics: "Dynamics", D=None, Kp=None, warm: bool = False,
                 floor: float | None = None, max_updates: int | None = None, abs_tol: float = 0.0,
-                rel_tol: float = 0.0):
+                rel_tol: float = 0.0, form: str = "default"):
         """K control steps of the states ``x0`` [B, ns] under ``dynamics``
         (pqp_plant_rollout, section 2j): step, x+ = (A x + Bu U) + Bd D, warm
         step, ... without leaving the device -- one launch for the one-wave
@@ -1115,14 +1127,19 @@ class Plant:
         the rows of ``self.Y``; later steps always start from the previous
         step's Y.  floor: Y is floored before every warm start (unlike
         ``step``'s, it does not make step 0 warm).  max_updates: per step.
-        abs_tol, rel_tol: ``step``'s gap tolerances, at every step."""
+        abs_tol, rel_tol: ``step``'s gap tolerances, at every step.
+        form: "default" (one launch for the one-wave plants, the chain for
+        ``horizon=True`` ones), "chain" or "fused" (one launch, either kind:
+        pqp_plant_rollout_form, section 2l); every form gives the same bits."""
+        if form not in self.ROLL_FORMS:
+            raise ValueError(f"Plant.rollout: form must be one of {sorted(self.ROLL_FORMS)}, not {form!r}")
         torch = self.torch
         f = dict(dtype=torch.float32, device=self.device)
         K = int(K)
         B = int(x0.shape[0]) if hasattr(x0, "shape") and len(x0.shape) == 2 else len(x0)
         if B <= 0 or K <= 0:
-            _check(lib().pqp_plant_rollout_tol(self._h, dynamics._h, B, K, None, None, 1, None, 0, 0.0, 1, *([None] * 6),
-                                               0.0, 0.0, None))
+            _check(lib().pqp_plant_rollout_form(self._h, dynamics._h, B, K, None, None, 1, None, 0, 0.0, 1, *([None] * 6),
+                                                0.0, 0.0, 0, None))
         if B != self.B or self._roll_K != K:
             keep_Y = B == self.B
             self.B, self._roll_K = B, K
@@ -1152,10 +1169,11 @@ class Plant:
         cap = self.max_updates if max_updates is None else int(max_updates)
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         self._inputs = (Dt, Kt, dynamics)  # alive until the next call: the launches are asynchronous
-        _check(lib().pqp_plant_rollout_tol(self._h, dynamics._h, B, K, p(self.X), p(Dt), d_steps,
-                                           None if Kt is None else p(Kt), int(bool(warm)),
-                                           0.0 if floor is None else float(floor), cap, p(self.Y), p(self.U), p(self.h),
-                                           p(self.status), p(self.Jp), p(self.Jd), float(abs_tol), float(rel_tol), stream))
+        _check(lib().pqp_plant_rollout_form(self._h, dynamics._h, B, K, p(self.X), p(Dt), d_steps,
+                                            None if Kt is None else p(Kt), int(bool(warm)),
+                                            0.0 if floor is None else float(floor), cap, p(self.Y), p(self.U), p(self.h),
+                                            p(self.status), p(self.Jp), p(self.Jd), float(abs_tol), float(rel_tol),
+                                            self.ROLL_FORMS[form], stream))
         return self
 
     def close(self):
