@@ -414,6 +414,17 @@ struct pqp_rowblock {
     pqp::RelayBlock relay;
 };
 
+// What both plant handles (pqp_plant, pqp_shared) keep of one plant: Qp_inv, Gp and Kp as given, and what
+// derive_plant_core makes of them once -- Qp, Qd, Gp Qp_inv, Theta and, where asked, sym: Qd bit-symmetric.
+namespace pqp {
+namespace {
+struct PlantCore {
+    DevBuf Qinv, Gp, Kp, Qp, Qd, GQ, theta;
+    int sym = 0;
+};
+}  // namespace
+}  // namespace pqp
+
 // One plant resident on its device (pqp_plant_*): the primal data as given,
 // what create derived from them, and the pointers a step hands its launch.
 // Immutable after create; a step writes only the caller's buffers.
@@ -423,7 +434,7 @@ struct pqp_plant {
     int dev = -1;            // the device it was made on (its steps run there)
     int slots[2] = {0, 0};   // workgroups resident at once: [0] the plain form, [1] the pipelined one (kind 2: both its one form)
     pqp::PlantMidFlags mid{};  // kind 2: what Qd alone decides in k_solve_mid2's staging
-    pqp::DevBuf Qinv, Gp, Kp, Qp, Qd, GQ, theta;
+    pqp::PlantCore core;
     pqp::DevBuf Fp1, Fp2, Fp3, Mp1, Mp2, Mp3, Mp4, Mp5, Mp6;
     pqp::PlantData data{};
     int roll_slots = 0;      // kind 1: workgroups of the fused rollout resident at once (0: the rollout is the chain)
@@ -446,8 +457,7 @@ struct pqp_shared {
     int N = 0, M = 0, ldq = 0, ldm = 0;
     int S = 0;     // states per workgroup (pqp_shared_states)
     int dev = -1;  // the device it was made on (its calls run there)
-    int sym = 0;   // Qd bit-symmetric: QdR is its own column-major copy
-    pqp::DevBuf Qinv, Gp, Kp, Qp, Qd, GQ, theta;
+    pqp::PlantCore core;  // core.sym: QdR is its own column-major copy
     pqp::DevBuf QdR, QdT, GpP, GpT, QinvT, QinvR, QpP, GQT;
     // pqp_shared_create_plant only (2i): the linear-term matrices k_step_shared reads; nd = ns = 0 without them
     int nd = 0, ns = 0;
@@ -1161,6 +1171,56 @@ int check_dims(int N, int M) {
     return PQP_OK;
 }
 
+// The device a create call (`fn` in messages) makes its handle on: `device`, or the current one for device < 0.
+int resolve_device(const char* fn, int device, int* dev) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return set_error(PQP_ERR_NO_DEVICE, "libpqp: no HIP device visible");
+    if (device < 0 && hipGetDevice(&device) != hipSuccess)
+        return set_error(PQP_ERR_NO_DEVICE, "libpqp: cannot query the current device");
+    if (device >= n) return set_error(PQP_ERR_ARG, "%s: device %d of %d", fn, device, n);
+    *dev = device;
+    return PQP_OK;
+}
+
+// A plant's core on the current device: the three inputs uploaded, and what every state shares derived once, by
+// the launchers the batched entry points use (B = 1).  want_sym: then Qd's bit symmetry, by their kernel too.
+// The stream is idle when it returns: the host arrays and the Gauss_Jordan scratch are free.
+int derive_plant_core(PlantCore& c, int N, int M, const float* Qp_inv, const float* Gp, const float* Kp, bool want_sym,
+                      hipStream_t s) {
+    PQP_TRY(upload(c.Qinv, Qp_inv, (size_t)M * M, s));
+    PQP_TRY(upload(c.Gp, Gp, (size_t)N * M, s));
+    PQP_TRY(upload(c.Kp, Kp, N, s));
+    PQP_TRY(c.Qp.floats((size_t)M * M));
+    PQP_TRY(c.Qd.floats((size_t)N * N));
+    PQP_TRY(c.GQ.floats((size_t)N * M));
+    PQP_TRY(c.theta.floats(N));
+    DevBuf aug, fac, symd;
+    PQP_TRY(aug.floats(gauss_jordan_aug_floats(M)));
+    PQP_TRY(fac.floats(M));
+    const long long nm = (long long)N * M, mm = (long long)M * M, nn = (long long)N * N;
+    PQP_HIP(launch_gauss_jordan_b(1, c.Qinv.f(), aug.f(), fac.f(), c.Qp.f(), M, s));                     // Qp :251
+    PQP_HIP(launch_matmul_seq_b(1, c.GQ.f(), c.Gp.f(), 0, c.Qinv.f(), 0, N, M, M, nm, mm, nm, s));      // Gp Qp_inv :492
+    PQP_HIP(launch_matmul_seq_b(1, c.Qd.f(), c.GQ.f(), 0, c.Gp.f(), 1, N, M, N, nm, nm, nn, s));        // Qd :440-455
+    PQP_HIP(launch_theta_rows(c.Qd.f(), N, N, N, c.theta.f(), s));                                      // Theta :503-519
+    int hsym = 0;
+    if (want_sym) {
+        PQP_TRY(symd.alloc(sizeof(int)));
+        PQP_HIP(launch_check_symmetric(1, c.Qd.f(), N, static_cast<int*>(symd.p), s));
+        PQP_HIP(hipMemcpyAsync(&hsym, symd.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    }
+    PQP_HIP(hipStreamSynchronize(s));
+    c.sym = hsym != 0 ? 1 : 0;
+    return PQP_OK;
+}
+
+// The three arrays both plant handles' _get download (each optional); the caller synchronises.
+int download_plant_core(const PlantCore& c, int N, int M, float* Qd, float* Qp, float* theta, hipStream_t s) {
+    if (Qd) PQP_TRY(download(Qd, c.Qd.p, (size_t)N * N, s));
+    if (Qp) PQP_TRY(download(Qp, c.Qp.p, (size_t)M * M, s));
+    if (theta) PQP_TRY(download(theta, c.theta.p, N, s));
+    return PQP_OK;
+}
+
 }  // namespace
 }  // namespace pqp
 
@@ -1181,11 +1241,7 @@ int pqp_problem_create_on(int device, void* stream, const float* Qd, const float
     PQP_TRY(check_dims(N, M));
     if (!Qd || !Fd || !Md || !Qp || !Qp_inv || !Fp || !Mp || !Gp || !Kp)
         return set_error(PQP_ERR_ARG, "pqp_problem_create: null input");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return set_error(PQP_ERR_NO_DEVICE, "libpqp: no HIP device visible");
-    if (device < 0 && hipGetDevice(&device) != hipSuccess)
-        return set_error(PQP_ERR_NO_DEVICE, "libpqp: cannot query the current device");
-    if (device >= n) return set_error(PQP_ERR_ARG, "pqp_problem_create_on: device %d of %d", device, n);
+    PQP_TRY(resolve_device("pqp_problem_create_on", device, &device));
     DeviceGuard on(device);
     PQP_TRY(ensure_device());
     std::unique_ptr<pqp_problem> P(new pqp_problem());
@@ -2047,11 +2103,7 @@ static int plant_create(const char* fn, bool horizon, int device, int N, int M, 
                          (N > 0 && M > 0 && N < (1 << 14) && M < (1 << 14)) ? plant_mid_lds_bytes(N, M) : (size_t)0);
     if (!Qp_inv || !Gp || !Kp || !Fp1 || !Fp2 || !Fp3 || !Mp1 || !Mp2 || !Mp3 || !Mp4 || !Mp5 || !Mp6)
         return set_error(PQP_ERR_ARG, "%s: null input", fn);
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return set_error(PQP_ERR_NO_DEVICE, "libpqp: no HIP device visible");
-    if (device < 0 && hipGetDevice(&device) != hipSuccess)
-        return set_error(PQP_ERR_NO_DEVICE, "libpqp: cannot query the current device");
-    if (device >= n) return set_error(PQP_ERR_ARG, "%s: device %d of %d", fn, device, n);
+    PQP_TRY(resolve_device(fn, device, &device));
     DeviceGuard on(device);
     PQP_TRY(ensure_device());
     hipStream_t s = lib_stream();
@@ -2059,9 +2111,6 @@ static int plant_create(const char* fn, bool horizon, int device, int N, int M, 
     P->N = N, P->M = M, P->nd = nd, P->ns = ns;
     P->kind = kind;
     P->dev = device;
-    PQP_TRY(upload(P->Qinv, Qp_inv, (size_t)M * M, s));
-    PQP_TRY(upload(P->Gp, Gp, (size_t)N * M, s));
-    PQP_TRY(upload(P->Kp, Kp, N, s));
     PQP_TRY(upload(P->Fp1, Fp1, (size_t)M * nd, s));
     PQP_TRY(upload(P->Fp2, Fp2, (size_t)M * ns, s));
     PQP_TRY(upload(P->Fp3, Fp3, M, s));
@@ -2071,19 +2120,9 @@ static int plant_create(const char* fn, bool horizon, int device, int N, int M, 
     PQP_TRY(upload(P->Mp4, Mp4, ns, s));
     PQP_TRY(upload(P->Mp5, Mp5, nd, s));
     PQP_TRY(upload(P->Mp6, Mp6, 1, s));
-    PQP_TRY(P->Qp.floats((size_t)M * M));
-    PQP_TRY(P->Qd.floats((size_t)N * N));
-    PQP_TRY(P->GQ.floats((size_t)N * M));
-    PQP_TRY(P->theta.floats(N));
-    // what every state shares, once, by the launchers the batched entry points use (B = 1)
-    DevBuf aug, fac;
-    PQP_TRY(aug.floats(gauss_jordan_aug_floats(M)));
-    PQP_TRY(fac.floats(M));
-    const long long nm = (long long)N * M, mm = (long long)M * M, nn = (long long)N * N;
-    PQP_HIP(launch_gauss_jordan_b(1, P->Qinv.f(), aug.f(), fac.f(), P->Qp.f(), M, s));                       // Qp :251
-    PQP_HIP(launch_matmul_seq_b(1, P->GQ.f(), P->Gp.f(), 0, P->Qinv.f(), 0, N, M, M, nm, mm, nm, s));      // Gp Qp_inv :492
-    PQP_HIP(launch_matmul_seq_b(1, P->Qd.f(), P->GQ.f(), 0, P->Gp.f(), 1, N, M, N, nm, nm, nn, s));        // Qd :440-455
-    PQP_HIP(launch_theta_rows(P->Qd.f(), N, N, N, P->theta.f(), s));                                       // Theta :503-519
+    // kind 2: with what k_solve_mid2 finds in Qd when it stages a problem, once -- its bit symmetry
+    PlantCore& c = P->core;
+    PQP_TRY(derive_plant_core(c, N, M, Qp_inv, Gp, Kp, kind == 2, s));  // (the host arrays are free after it)
     for (int pipe = 0; pipe < 2; ++pipe) {
         P->slots[pipe] = kind == 2 ? plant_mid_resident_wgs(N, M) : plant_resident_wgs(N, M, nd, ns, pipe != 0);
         if (P->slots[pipe] <= 0) {
@@ -2106,31 +2145,23 @@ static int plant_create(const char* fn, bool horizon, int device, int N, int M, 
             P->roll_mid_slots = 0;
         }
     }
-    if (kind == 2) {
-        // what k_solve_mid2 finds in Qd when it stages a problem, once: bit symmetry by the batched
-        // entry points' kernel, NaN / inf by a scan of the host copy
-        DevBuf symd;
-        PQP_TRY(symd.alloc(sizeof(int)));
-        PQP_HIP(launch_check_symmetric(1, P->Qd.f(), N, static_cast<int*>(symd.p), s));
-        int hsym = 0;
-        PQP_HIP(hipMemcpyAsync(&hsym, symd.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    if (kind == 2) {  // the rest of what k_solve_mid2 finds in Qd: NaN / inf, by a scan of the host copy
         std::vector<float> hq((size_t)N * N);
-        PQP_TRY(download(hq.data(), P->Qd.p, hq.size(), s));
+        PQP_TRY(download(hq.data(), c.Qd.p, hq.size(), s));
         PQP_HIP(hipStreamSynchronize(s));
         bool nan = false, inf = false;
         for (float q : hq) {
             nan = nan || q != q;
             inf = inf || std::fabs(q) == std::numeric_limits<float>::infinity();
         }
-        P->mid.sym = hsym != 0 ? 1 : 0;
+        P->mid.sym = c.sym;
         P->mid.fast = nan ? 0 : 1;
         P->mid.qfinite = (!nan && !inf) ? 1 : 0;
     }
-    PQP_HIP(hipStreamSynchronize(s));  // the host arrays and the Gauss_Jordan scratch are free after it
     PlantData& d = P->data;
     d.N = N, d.M = M, d.nd = nd, d.ns = ns;
-    d.Qd = P->Qd.f(), d.Gp = P->Gp.f(), d.Qp = P->Qp.f(), d.Qinv = P->Qinv.f(), d.Kp = P->Kp.f();
-    d.theta = P->theta.f(), d.GQ = P->GQ.f();
+    d.Qd = c.Qd.f(), d.Gp = c.Gp.f(), d.Qp = c.Qp.f(), d.Qinv = c.Qinv.f(), d.Kp = c.Kp.f();
+    d.theta = c.theta.f(), d.GQ = c.GQ.f();
     d.Fp1 = P->Fp1.f(), d.Fp2 = P->Fp2.f(), d.Fp3 = P->Fp3.f();
     d.Mp1 = P->Mp1.f(), d.Mp2 = P->Mp2.f(), d.Mp3 = P->Mp3.f();
     d.Mp4 = P->Mp4.f(), d.Mp5 = P->Mp5.f(), d.Mp6 = P->Mp6.f();
@@ -2165,9 +2196,7 @@ int pqp_plant_get(pqp_plant* p, float* Qd, float* Qp, float* theta) {
     DeviceGuard on(p->dev);
     PQP_TRY(ensure_device());
     hipStream_t s = lib_stream();
-    if (Qd) PQP_TRY(download(Qd, p->Qd.p, (size_t)p->N * p->N, s));
-    if (Qp) PQP_TRY(download(Qp, p->Qp.p, (size_t)p->M * p->M, s));
-    if (theta) PQP_TRY(download(theta, p->theta.p, p->N, s));
+    PQP_TRY(download_plant_core(p->core, p->N, p->M, Qd, Qp, theta, s));
     PQP_HIP(hipStreamSynchronize(s));
     return PQP_OK;
 }
@@ -2177,12 +2206,17 @@ long long pqp_plant_max_updates(const pqp_plant* p) {
     return pqp::batch_chunk_for(p->N, p->M);
 }
 
+// A kind-2 plant's flags as a launch takes them: create's, and the tuning knob mid2_dense as it is now.
+static PlantMidFlags plant_mid_flags(const pqp_plant& p) {
+    PlantMidFlags F = p.mid;
+    F.dense = g_tune.mid2_dense ? 1 : 0;
+    return F;
+}
+
 // One step's launch on the plant's device (current): the kind's kernel, at the tuning knobs' form.
 static int plant_launch_step(const pqp_plant& p, const PlantStep& S, hipStream_t s) {
     if (p.kind == 2) {  // the one-workgroup step: plant_pipe has no meaning for it
-        PlantMidFlags F = p.mid;
-        F.dense = g_tune.mid2_dense ? 1 : 0;
-        PQP_HIP(launch_plant_step_mid(p.data, S, F, p.slots[0], s));
+        PQP_HIP(launch_plant_step_mid(p.data, S, plant_mid_flags(p), p.slots[0], s));
         return PQP_OK;
     }
     const bool pipe = g_plant_pipe != 0;
@@ -2199,19 +2233,31 @@ static int check_tols(const char* fn, float abs_tol, float rel_tol) {
     return PQP_OK;
 }
 
+// What the step, solve and rollout entry points check alike, in two parts, since each has checks of its own between
+// them: the handle (`what` names it) and B; then max_updates against one launch's budget (`budget_fn` reports it,
+// `per` is what it bounds: a launch or a rollout's step).
+static int check_states(const char* fn, const void* handle, const char* what, int B) {
+    if (!handle) return set_error(PQP_ERR_ARG, "%s: null %s", fn, what);
+    if (B <= 0) return set_error(PQP_ERR_ARG, "%s: B = %d states", fn, B);
+    return PQP_OK;
+}
+static int check_budget(const char* fn, long long max_updates, int N, int M, const char* budget_fn, const char* per) {
+    const long long cap = pqp::batch_chunk_for(N, M);
+    if (max_updates < 1 || max_updates > cap)
+        return set_error(PQP_ERR_ARG, "%s: max_updates = %lld is outside 1 .. %lld (%s: one %s's budget)", fn,
+                         max_updates, cap, budget_fn, per);
+    return PQP_OK;
+}
+
 // pqp_plant_step (fn names the caller in messages; tolerances 0, 0) and pqp_plant_step_tol
 static int plant_step(const char* fn, pqp_plant* p, int B, const float* d_x, const float* d_D, const float* d_Kp,
                       int warm, long long max_updates, float* d_Y, float* d_U, long long* d_h, int* d_status,
                       float* d_Fp, float* d_Mp, float* d_Fd, float* d_Md, float* d_Jp, float* d_Jd, float abs_tol,
                       float rel_tol, void* stream) {
     PQP_TRY(check_tols(fn, abs_tol, rel_tol));
-    if (!p) return set_error(PQP_ERR_ARG, "%s: null plant", fn);
-    if (B <= 0) return set_error(PQP_ERR_ARG, "%s: B = %d states", fn, B);
+    PQP_TRY(check_states(fn, p, "plant", B));
     if (!d_x || !d_D || !d_Y || !d_U) return set_error(PQP_ERR_ARG, "%s: null d_x, d_D, d_Y or d_U", fn);
-    const long long cap = pqp::batch_chunk_for(p->N, p->M);
-    if (max_updates < 1 || max_updates > cap)
-        return set_error(PQP_ERR_ARG, "%s: max_updates = %lld is outside 1 .. %lld (pqp_plant_max_updates: "
-                                      "one launch's budget)", fn, max_updates, cap);
+    PQP_TRY(check_budget(fn, max_updates, p->N, p->M, "pqp_plant_max_updates", "launch"));
     PlantStep S{};
     S.B = B;
     S.warm = warm ? 1 : 0;
@@ -2250,11 +2296,7 @@ int pqp_dynamics_create(int device, int ns, int M, int nd, const float* A, const
         return set_error(PQP_ERR_ARG, "pqp_dynamics_create: (ns=%d, M=%d, nd=%d) is outside 1 <= ns, nd <= 64, "
                                       "1 <= M <= %d", ns, M, nd, kDynMaxM);
     if (!A || !Bu || !Bd) return set_error(PQP_ERR_ARG, "pqp_dynamics_create: null input");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return set_error(PQP_ERR_NO_DEVICE, "libpqp: no HIP device visible");
-    if (device < 0 && hipGetDevice(&device) != hipSuccess)
-        return set_error(PQP_ERR_NO_DEVICE, "libpqp: cannot query the current device");
-    if (device >= n) return set_error(PQP_ERR_ARG, "pqp_dynamics_create: device %d of %d", device, n);
+    PQP_TRY(resolve_device("pqp_dynamics_create", device, &device));
     DeviceGuard on(device);
     PQP_TRY(ensure_device());
     hipStream_t s = lib_stream();
@@ -2287,8 +2329,7 @@ int pqp_dynamics_destroy(pqp_dynamics* d) {
 
 int pqp_dynamics_advance(const pqp_dynamics* d, int B, const float* d_x, const float* d_U, const float* d_D,
                          float* d_xnext, void* stream) {
-    if (!d) return set_error(PQP_ERR_ARG, "pqp_dynamics_advance: null dynamics");
-    if (B <= 0) return set_error(PQP_ERR_ARG, "pqp_dynamics_advance: B = %d states", B);
+    PQP_TRY(check_states("pqp_dynamics_advance", d, "dynamics", B));
     if (!d_x || !d_U || !d_D || !d_xnext)
         return set_error(PQP_ERR_ARG, "pqp_dynamics_advance: null d_x, d_U, d_D or d_xnext");
     if (d_xnext == d_x) return set_error(PQP_ERR_ARG, "pqp_dynamics_advance: d_xnext aliases d_x");
@@ -2320,16 +2361,12 @@ static int plant_rollout(const char* fn, pqp_plant* p, const pqp_dynamics* dyn, 
         return set_error(PQP_ERR_ARG, "%s: form = %d is none of PQP_ROLL_DEFAULT, PQP_ROLL_CHAIN, PQP_ROLL_FUSED", fn,
                          form);
     if (!p) return set_error(PQP_ERR_ARG, "%s: null plant", fn);
-    if (!dyn) return set_error(PQP_ERR_ARG, "%s: null dynamics", fn);
-    if (B <= 0) return set_error(PQP_ERR_ARG, "%s: B = %d states", fn, B);
+    PQP_TRY(check_states(fn, dyn, "dynamics", B));
     if (K <= 0) return set_error(PQP_ERR_ARG, "%s: K = %d steps", fn, K);
     if (D_steps != 1 && D_steps != K)
         return set_error(PQP_ERR_ARG, "%s: D_steps = %d is neither 1 nor K = %d", fn, D_steps, K);
     if (!d_X || !d_D || !d_Y || !d_U) return set_error(PQP_ERR_ARG, "%s: null d_X, d_D, d_Y or d_U", fn);
-    const long long cap = pqp::batch_chunk_for(p->N, p->M);
-    if (max_updates < 1 || max_updates > cap)
-        return set_error(PQP_ERR_ARG, "%s: max_updates = %lld is outside 1 .. %lld (pqp_plant_max_updates: "
-                                      "one step's budget)", fn, max_updates, cap);
+    PQP_TRY(check_budget(fn, max_updates, p->N, p->M, "pqp_plant_max_updates", "step"));
     if (dyn->ns != p->ns || dyn->M != p->M || dyn->nd != p->nd)
         return set_error(PQP_ERR_ARG, "%s: the dynamics' (ns=%d, M=%d, nd=%d) are not the plant's "
                                       "(ns=%d, M=%d, nd=%d)", fn, dyn->ns, dyn->M, dyn->nd, p->ns, p->M, p->nd);
@@ -2359,9 +2396,7 @@ static int plant_rollout(const char* fn, pqp_plant* p, const pqp_dynamics* dyn, 
         S.U = d_U, S.h = d_h, S.status = d_status, S.Jp = d_Jp, S.Jd = d_Jd;
         const PlantRoll R{K, D_steps, y_floor, d_X, dyn->data};
         if (p->kind == 2) {
-            PlantMidFlags F = p->mid;
-            F.dense = g_tune.mid2_dense ? 1 : 0;
-            PQP_HIP(launch_plant_roll_mid(p->data, S, F, R, p->roll_mid_slots, s));
+            PQP_HIP(launch_plant_roll_mid(p->data, S, plant_mid_flags(*p), R, p->roll_mid_slots, s));
         } else {
             PQP_HIP(launch_plant_roll(p->data, S, R, p->roll_slots, s));
         }
@@ -2445,39 +2480,15 @@ static int shared_create(const char* fn, int device, int N, int M, const float* 
     if (lin && (!lin->Fp1 || !lin->Fp2 || !lin->Fp3 || !lin->Mp1 || !lin->Mp2 || !lin->Mp3 || !lin->Mp4 || !lin->Mp5 ||
                 !lin->Mp6))
         return set_error(PQP_ERR_ARG, "%s: null input", fn);
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return set_error(PQP_ERR_NO_DEVICE, "libpqp: no HIP device visible");
-    if (device < 0 && hipGetDevice(&device) != hipSuccess)
-        return set_error(PQP_ERR_NO_DEVICE, "libpqp: cannot query the current device");
-    if (device >= n) return set_error(PQP_ERR_ARG, "%s: device %d of %d", fn, device, n);
+    PQP_TRY(resolve_device(fn, device, &device));
     DeviceGuard on(device);
     PQP_TRY(ensure_device());
     hipStream_t s = lib_stream();
     std::unique_ptr<pqp_shared> P(new pqp_shared());
     const int ldq = round4(N), ldm = round4(M);
     P->N = N, P->M = M, P->ldq = ldq, P->ldm = ldm, P->S = S, P->dev = device;
-    PQP_TRY(upload(P->Qinv, Qp_inv, (size_t)M * M, s));
-    PQP_TRY(upload(P->Gp, Gp, (size_t)N * M, s));
-    PQP_TRY(upload(P->Kp, Kp, N, s));
-    PQP_TRY(P->Qp.floats((size_t)M * M));
-    PQP_TRY(P->Qd.floats((size_t)N * N));
-    PQP_TRY(P->GQ.floats((size_t)N * M));
-    PQP_TRY(P->theta.floats(N));
-    // what every state shares, once, by the launchers plant_create and the batched entry points use (B = 1)
-    DevBuf aug, fac, symd;
-    PQP_TRY(aug.floats(gauss_jordan_aug_floats(M)));
-    PQP_TRY(fac.floats(M));
-    PQP_TRY(symd.alloc(sizeof(int)));
-    const long long nm = (long long)N * M, mm = (long long)M * M, nn = (long long)N * N;
-    PQP_HIP(launch_gauss_jordan_b(1, P->Qinv.f(), aug.f(), fac.f(), P->Qp.f(), M, s));                       // Qp :251
-    PQP_HIP(launch_matmul_seq_b(1, P->GQ.f(), P->Gp.f(), 0, P->Qinv.f(), 0, N, M, M, nm, mm, nm, s));      // Gp Qp_inv :492
-    PQP_HIP(launch_matmul_seq_b(1, P->Qd.f(), P->GQ.f(), 0, P->Gp.f(), 1, N, M, N, nm, nm, nn, s));        // Qd :440-455
-    PQP_HIP(launch_theta_rows(P->Qd.f(), N, N, N, P->theta.f(), s));                                       // Theta :503-519
-    PQP_HIP(launch_check_symmetric(1, P->Qd.f(), N, static_cast<int*>(symd.p), s));
-    int hsym = 0;
-    PQP_HIP(hipMemcpyAsync(&hsym, symd.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    PQP_HIP(hipStreamSynchronize(s));
-    P->sym = hsym != 0 ? 1 : 0;
+    PlantCore& c = P->core;
+    PQP_TRY(derive_plant_core(c, N, M, Qp_inv, Gp, Kp, true, s));
     // the kernels' layouts: rows padded to a multiple of 4 floats (zero-filled), k-major for each product
     PQP_TRY(P->QdR.floats((size_t)N * ldq));
     PQP_TRY(P->GpP.floats((size_t)N * ldm));
@@ -2486,17 +2497,17 @@ static int shared_create(const char* fn, int device, int N, int M, const float* 
     PQP_TRY(P->QinvR.floats((size_t)M * ldm));
     PQP_TRY(P->QpP.floats((size_t)M * ldm));
     PQP_TRY(P->GQT.floats((size_t)M * ldq));
-    PQP_HIP(launch_shared_layout(P->Qd.f(), N, N, 0, P->QdR.f(), ldq, s));
-    if (!P->sym) {  // a bit-symmetric Qd is its own column-major copy
+    PQP_HIP(launch_shared_layout(c.Qd.f(), N, N, 0, P->QdR.f(), ldq, s));
+    if (!c.sym) {  // a bit-symmetric Qd is its own column-major copy
         PQP_TRY(P->QdT.floats((size_t)N * ldq));
-        PQP_HIP(launch_shared_layout(P->Qd.f(), N, N, 1, P->QdT.f(), ldq, s));
+        PQP_HIP(launch_shared_layout(c.Qd.f(), N, N, 1, P->QdT.f(), ldq, s));
     }
-    PQP_HIP(launch_shared_layout(P->Gp.f(), N, M, 0, P->GpP.f(), ldm, s));
-    PQP_HIP(launch_shared_layout(P->Gp.f(), M, N, 1, P->GpT.f(), ldq, s));
-    PQP_HIP(launch_shared_layout(P->Qinv.f(), M, M, 1, P->QinvT.f(), ldm, s));
-    PQP_HIP(launch_shared_layout(P->Qinv.f(), M, M, 0, P->QinvR.f(), ldm, s));
-    PQP_HIP(launch_shared_layout(P->Qp.f(), M, M, 0, P->QpP.f(), ldm, s));
-    PQP_HIP(launch_shared_layout(P->GQ.f(), M, N, 1, P->GQT.f(), ldq, s));
+    PQP_HIP(launch_shared_layout(c.Gp.f(), N, M, 0, P->GpP.f(), ldm, s));
+    PQP_HIP(launch_shared_layout(c.Gp.f(), M, N, 1, P->GpT.f(), ldq, s));
+    PQP_HIP(launch_shared_layout(c.Qinv.f(), M, M, 1, P->QinvT.f(), ldm, s));
+    PQP_HIP(launch_shared_layout(c.Qinv.f(), M, M, 0, P->QinvR.f(), ldm, s));
+    PQP_HIP(launch_shared_layout(c.Qp.f(), M, M, 0, P->QpP.f(), ldm, s));
+    PQP_HIP(launch_shared_layout(c.GQ.f(), M, N, 1, P->GQT.f(), ldq, s));
     DevBuf in[5];  // the uploaded Fp1, Fp2, Mp1, Mp2, Mp3, alive until their padded copies are made
     if (lin) {
         // the step's matrices: k-major for its products, rows padded like the rest
@@ -2522,7 +2533,7 @@ static int shared_create(const char* fn, int device, int N, int M, const float* 
         PQP_HIP(launch_shared_layout(in[3].f(), nd, ns, 0, P->Mp2P.f(), ldx, s));
         PQP_HIP(launch_shared_layout(in[4].f(), nd, nd, 0, P->Mp3P.f(), ldd, s));
     }
-    PQP_HIP(hipStreamSynchronize(s));  // the host arrays and the Gauss_Jordan scratch are free after it
+    PQP_HIP(hipStreamSynchronize(s));  // the host arrays and the uploaded copies are free after it
     *out = P.release();
     return PQP_OK;
 }
@@ -2544,23 +2555,30 @@ int pqp_shared_get(pqp_shared* p, float* Qd, float* Qp, float* theta, float* GQ,
     DeviceGuard on(p->dev);
     PQP_TRY(ensure_device());
     hipStream_t s = lib_stream();
-    if (Qd) PQP_TRY(download(Qd, p->Qd.p, (size_t)p->N * p->N, s));
-    if (Qp) PQP_TRY(download(Qp, p->Qp.p, (size_t)p->M * p->M, s));
-    if (theta) PQP_TRY(download(theta, p->theta.p, p->N, s));
-    if (GQ) PQP_TRY(download(GQ, p->GQ.p, (size_t)p->N * p->M, s));
+    PQP_TRY(download_plant_core(p->core, p->N, p->M, Qd, Qp, theta, s));
+    if (GQ) PQP_TRY(download(GQ, p->core.GQ.p, (size_t)p->N * p->M, s));
     PQP_HIP(hipStreamSynchronize(s));
-    if (sym_out) *sym_out = p->sym;
+    if (sym_out) *sym_out = p->core.sym;
     return PQP_OK;
+}
+
+// The handle's part of a solve's or a step's SharedSolveCore: the plant's layouts and the shape.
+static SharedSolveCore shared_core_args(const pqp_shared& p) {
+    SharedSolveCore a{};
+    const int sym = p.core.sym;
+    a.QdR = p.QdR.f(), a.QdT = sym ? p.QdR.f() : p.QdT.f(), a.theta = p.core.theta.f();
+    a.GpP = p.GpP.f(), a.GpT = p.GpT.f(), a.QinvT = p.QinvT.f(), a.QpP = p.QpP.f(), a.Kp = p.core.Kp.f();
+    a.N = p.N, a.M = p.M, a.ldq = p.ldq, a.ldm = p.ldm, a.sym = sym;
+    return a;
 }
 
 int pqp_shared_relinearize(pqp_shared* p, int B, const float* d_Fp, const float* d_Mp, const float* d_Kp, float* d_Fd,
                            float* d_Md, void* stream) {
-    if (!p) return set_error(PQP_ERR_ARG, "pqp_shared_relinearize: null handle");
-    if (B <= 0) return set_error(PQP_ERR_ARG, "pqp_shared_relinearize: B = %d states", B);
+    PQP_TRY(check_states("pqp_shared_relinearize", p, "handle", B));
     if (!d_Fp || !d_Mp || !d_Fd || !d_Md)
         return set_error(PQP_ERR_ARG, "pqp_shared_relinearize: null d_Fp, d_Mp, d_Fd or d_Md");
     SharedRelinArgs a{};
-    a.GQT = p->GQT.f(), a.QinvR = p->QinvR.f(), a.Kp = p->Kp.f();
+    a.GQT = p->GQT.f(), a.QinvR = p->QinvR.f(), a.Kp = p->core.Kp.f();
     a.Fp = d_Fp, a.Mp = d_Mp, a.KpB = d_Kp, a.Fd = d_Fd, a.Md = d_Md;
     a.N = p->N, a.M = p->M, a.ldq = p->ldq, a.ldm = p->ldm, a.B = B;
     DeviceGuard on(p->dev);
@@ -2574,8 +2592,7 @@ static int shared_solve(const char* fn, pqp_shared* p, int B, const float* d_Fd,
                         float* d_U, long long* d_h, int* d_status, float* d_Jp, float* d_Jd, float abs_tol,
                         float rel_tol, void* stream) {
     PQP_TRY(check_tols(fn, abs_tol, rel_tol));
-    if (!p) return set_error(PQP_ERR_ARG, "%s: null handle", fn);
-    if (B <= 0) return set_error(PQP_ERR_ARG, "%s: B = %d states", fn, B);
+    PQP_TRY(check_states(fn, p, "handle", B));
     if (!d_Fd || !d_Md || !d_Fp || !d_Mp || !d_Y || !d_U)
         return set_error(PQP_ERR_ARG, "%s: null d_Fd, d_Md, d_Fp, d_Mp, d_Y or d_U", fn);
     DeviceGuard on(p->dev);
@@ -2585,14 +2602,12 @@ static int shared_solve(const char* fn, pqp_shared* p, int B, const float* d_Fd,
     DevBuf state, pending;
     PQP_TRY(state.alloc(sizeof(SharedSolveState) * (size_t)B));
     PQP_TRY(pending.alloc(sizeof(int)));
-    SharedSolveArgs a{};
-    a.QdR = p->QdR.f(), a.QdT = p->sym ? p->QdR.f() : p->QdT.f(), a.theta = p->theta.f();
-    a.GpP = p->GpP.f(), a.GpT = p->GpT.f(), a.QinvT = p->QinvT.f(), a.QpP = p->QpP.f(), a.Kp = p->Kp.f();
+    SharedSolveArgs a{shared_core_args(*p)};  // (built in place; the tolerances after it zeroed)
     a.Fd = d_Fd, a.Md = d_Md, a.Fp = d_Fp, a.Mp = d_Mp, a.KpB = d_Kp;
     a.Y = d_Y, a.U = d_U, a.h = d_h, a.status = d_status, a.Jp = d_Jp, a.Jd = d_Jd;
     a.st = static_cast<SharedSolveState*>(state.p);
     a.pending = static_cast<int*>(pending.p);
-    a.N = p->N, a.M = p->M, a.ldq = p->ldq, a.ldm = p->ldm, a.B = B, a.sym = p->sym;
+    a.B = B;
     a.max_updates = max_updates;
     a.abs_tol = abs_tol, a.rel_tol = rel_tol;
     a.chunk = pqp::batch_chunk_for(p->N, p->M);
@@ -2647,24 +2662,18 @@ static int shared_step(const char* fn, pqp_shared* p, int B, const float* d_x, c
                        float* d_Fp, float* d_Mp, float* d_Fd, float* d_Md, float* d_Jp, float* d_Jd, float abs_tol,
                        float rel_tol, void* stream) {
     PQP_TRY(check_tols(fn, abs_tol, rel_tol));
-    if (!p) return set_error(PQP_ERR_ARG, "%s: null handle", fn);
-    if (B <= 0) return set_error(PQP_ERR_ARG, "%s: B = %d states", fn, B);
+    PQP_TRY(check_states(fn, p, "handle", B));
     if (!d_x || !d_D || !d_Y || !d_U || !d_Fp || !d_Fd)
         return set_error(PQP_ERR_ARG, "%s: null d_x, d_D, d_Y, d_U, d_Fp or d_Fd", fn);
     if (p->nd == 0)
         return set_error(PQP_ERR_ARG, "%s: the handle was made by pqp_shared_create and has no plant "
                                       "matrices (use pqp_shared_create_plant)", fn);
-    const long long cap = pqp::batch_chunk_for(p->N, p->M);
-    if (max_updates < 1 || max_updates > cap)
-        return set_error(PQP_ERR_ARG, "%s: max_updates = %lld is outside 1 .. %lld "
-                                      "(pqp_shared_max_updates: one launch's budget)", fn, max_updates, cap);
-    SharedStepArgs t{};
+    PQP_TRY(check_budget(fn, max_updates, p->N, p->M, "pqp_shared_max_updates", "launch"));
+    SharedStepArgs t{shared_core_args(*p)};  // (t.solve, built in place; every member after it zeroed)
     SharedSolveCore& a = t.solve;
-    a.QdR = p->QdR.f(), a.QdT = p->sym ? p->QdR.f() : p->QdT.f(), a.theta = p->theta.f();
-    a.GpP = p->GpP.f(), a.GpT = p->GpT.f(), a.QinvT = p->QinvT.f(), a.QpP = p->QpP.f(), a.Kp = p->Kp.f();
     a.Fd = d_Fd, a.Fp = d_Fp, a.KpB = d_Kp;  // Md, Mp: the kernel's own words
     a.Y = d_Y, a.U = d_U, a.h = d_h, a.status = d_status, a.Jp = d_Jp, a.Jd = d_Jd;
-    a.N = p->N, a.M = p->M, a.ldq = p->ldq, a.ldm = p->ldm, a.B = B, a.sym = p->sym;
+    a.B = B;
     a.max_updates = max_updates;
     t.abs_tol = abs_tol, t.rel_tol = rel_tol;
     a.chunk = max_updates;  // every state finishes within it

@@ -43,8 +43,8 @@ bool plant_shape_ok(int N, int M, int nd, int ns);
 // bytes of LDS one workgroup (one wave) of the step takes
 size_t plant_lds_bytes(int N, int M, int nd, int ns);
 // NMAX | MMAX << 8 of the k_plant_step instantiation that the launches below pick for (N, M) -- the step in
-// both forms and the fused rollout, under either stopping rule; 0 if they would not all pick the same one.
-// Host only: it compares the dispatch's kernel pointers (tests: which cases reach which of the 15 widths).
+// both forms and the fused rollout, under either stopping rule: the one choice their dispatch switches over.
+// Host only (tests: which cases reach which of the 15 widths).
 int plant_widths(int N, int M);
 // Workgroups of the form `pipe` resident on the current device at once (its
 // CUs times the occupancy of the shape's instantiation); 0 with the error left
@@ -117,8 +117,8 @@ bool plant_mid_shape_ok(int N, int M, int nd, int ns);
 size_t plant_mid_lds_bytes(int N, int M);
 // threads | pair << 16 | lean << 17 | band << 18 of the k_plant_step_mid build that the launch below picks for N,
 // under either stopping rule: the workgroup's threads, lane sides (<1024, true>), the lean rings (<384, false, 6>),
-// the band table (every build but N <= 64's); 0 if the two rules would not pick the same build.  Host only: it
-// compares the dispatch's kernel pointers (tests: which cases reach which of the four builds).
+// the band table (every build but N <= 64's): the one choice the dispatch of the step and of the fused rollout
+// switches over.  Host only (tests: which cases reach which of the four builds).
 int plant_mid_build(int N);
 // Workgroups resident on the current device at once; 0 with the error left in
 // hipGetLastError.  Queried once per plant, never in a step.

@@ -208,80 +208,74 @@ __global__ void __launch_bounds__(256) k_plant_floor(float* Y, size_t n, float y
     }
 }
 
-typedef void (*PlantKernel)(PlantData, PlantStep);
+// ---- the dispatch: (N, M) to one of the 15 widths, picked once; then the kernel of a form and a rule ----
+// The unrolled sums run to the next instantiated width >= N (>= M), as launch_tiny_grid's.
+struct PlantWidths {
+    int nmax, mmax;
+};
+inline PlantWidths plant_pick_widths(int N, int M) {
+    return {N <= 8 ? 8 : N <= 16 ? 16 : N <= 24 ? 24 : N <= 28 ? 28 : 32, M <= 8 ? 8 : M <= 16 ? 16 : 32};
+}
+
+// PIPE: the pipelined step; ROLL: the fused rollout; neither: the plain step
+template <bool PIPE, bool ROLL>
+using PlantKernel = void (*)(PlantData, std::conditional_t<ROLL, PlantRollStep, PlantStep>);
 
 // tol: k_plant_step_tol, where the step has a positive tolerance (plant_step_tol)
-template <int NMAX, int MMAX, bool PIPE>
-PlantKernel plant_kernel_t(bool tol) {
-    return tol ? k_plant_step_tol<NMAX, MMAX, PIPE> : k_plant_step<NMAX, MMAX, PIPE>;
+template <bool PIPE, bool ROLL, int NMAX, int MMAX>
+PlantKernel<PIPE, ROLL> plant_kernel_at(bool tol) {
+    return tol ? k_plant_step_tol<NMAX, MMAX, PIPE, ROLL> : k_plant_step<NMAX, MMAX, PIPE, ROLL>;
 }
-template <int NMAX, bool PIPE>
-PlantKernel plant_kernel_m(int M, bool tol) {
-    if (M <= 8) return plant_kernel_t<NMAX, 8, PIPE>(tol);
-    if (M <= 16) return plant_kernel_t<NMAX, 16, PIPE>(tol);
-    return plant_kernel_t<NMAX, 32, PIPE>(tol);
+template <bool PIPE, bool ROLL, int NMAX>
+PlantKernel<PIPE, ROLL> plant_kernel_m(int mmax, bool tol) {
+    switch (mmax) {
+        case 8: return plant_kernel_at<PIPE, ROLL, NMAX, 8>(tol);
+        case 16: return plant_kernel_at<PIPE, ROLL, NMAX, 16>(tol);
+        default: return plant_kernel_at<PIPE, ROLL, NMAX, 32>(tol);
+    }
 }
-template <bool PIPE>
-PlantKernel plant_kernel_n(int N, int M, bool tol) {
-    // the unrolled sums run to the next instantiated width >= N (>= M), as launch_tiny_grid's
-    if (N <= 8) return plant_kernel_m<8, PIPE>(M, tol);
-    if (N <= 16) return plant_kernel_m<16, PIPE>(M, tol);
-    if (N <= 24) return plant_kernel_m<24, PIPE>(M, tol);
-    if (N <= 28) return plant_kernel_m<28, PIPE>(M, tol);
-    return plant_kernel_m<32, PIPE>(M, tol);
+template <bool PIPE, bool ROLL>
+PlantKernel<PIPE, ROLL> plant_kernel(int N, int M, bool tol = false) {
+    const PlantWidths w = plant_pick_widths(N, M);
+    switch (w.nmax) {
+        case 8: return plant_kernel_m<PIPE, ROLL, 8>(w.mmax, tol);
+        case 16: return plant_kernel_m<PIPE, ROLL, 16>(w.mmax, tol);
+        case 24: return plant_kernel_m<PIPE, ROLL, 24>(w.mmax, tol);
+        case 28: return plant_kernel_m<PIPE, ROLL, 28>(w.mmax, tol);
+        default: return plant_kernel_m<PIPE, ROLL, 32>(w.mmax, tol);
+    }
 }
-PlantKernel plant_kernel(int N, int M, bool pipe, bool tol = false) {
-    return pipe ? plant_kernel_n<true>(N, M, tol) : plant_kernel_n<false>(N, M, tol);
-}
-
-typedef void (*RollKernel)(PlantData, PlantRollStep);
-
-template <int NMAX, int MMAX>
-RollKernel roll_kernel_t(bool tol) {
-    return tol ? k_plant_step_tol<NMAX, MMAX, false, true> : k_plant_step<NMAX, MMAX, false, true>;
-}
-template <int NMAX>
-RollKernel roll_kernel_m(int M, bool tol) {
-    if (M <= 8) return roll_kernel_t<NMAX, 8>(tol);
-    if (M <= 16) return roll_kernel_t<NMAX, 16>(tol);
-    return roll_kernel_t<NMAX, 32>(tol);
-}
-RollKernel roll_kernel(int N, int M, bool tol = false) {  // plant_kernel's widths
-    if (N <= 8) return roll_kernel_m<8>(M, tol);
-    if (N <= 16) return roll_kernel_m<16>(M, tol);
-    if (N <= 24) return roll_kernel_m<24>(M, tol);
-    if (N <= 28) return roll_kernel_m<28>(M, tol);
-    return roll_kernel_m<32>(M, tol);
+PlantKernel<false, false> plant_step_kernel(int N, int M, bool pipe, bool tol = false) {
+    return pipe ? plant_kernel<true, false>(N, M, tol) : plant_kernel<false, false>(N, M, tol);
 }
 
-// plant_widths: the dispatch above asked which instantiation it picks -- true where the plain step, the
-// pipelined step and the rollout of (N, M), under either rule, are all the <NMAX, MMAX> kernels
-template <int NMAX, int MMAX>
-bool plant_runs_at(int N, int M) {
-    for (int tol = 0; tol < 2; ++tol)
-        if (plant_kernel(N, M, false, tol) != plant_kernel_t<NMAX, MMAX, false>(tol) ||
-            plant_kernel(N, M, true, tol) != plant_kernel_t<NMAX, MMAX, true>(tol) ||
-            roll_kernel(N, M, tol) != roll_kernel_t<NMAX, MMAX>(tol))
-            return false;
-    return true;
+size_t plant_roll_lds_bytes(int N, int M, int nd, int ns) {
+    return plant_lds_bytes(N, M, nd, ns) + plant_dyn_lds_bytes(M, nd, ns);
 }
-template <int NMAX>
-int plant_widths_n(int N, int M) {
-    if (plant_runs_at<NMAX, 8>(N, M)) return NMAX | 8 << 8;
-    if (plant_runs_at<NMAX, 16>(N, M)) return NMAX | 16 << 8;
-    if (plant_runs_at<NMAX, 32>(N, M)) return NMAX | 32 << 8;
-    return 0;
+
+// ---- what every launch of the plant family shares (pqp_plant_mid.hip's too: it is included after this file) ----
+// Workgroups of `kernel` (`threads` each, `lds` bytes of dynamic LDS) resident on the current device at once: its
+// CUs times the kernel's occupancy; 0 with the error left in hipGetLastError.  What every *_resident_wgs asks, of
+// its shape's instantiation.
+int resident_wgs(const void* kernel, int threads, size_t lds) {
+    int dev = 0, cus = 0, per_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds) != hipSuccess) return 0;
+    return cus * per_cu;
+}
+// The grid of a launch over B states (or groups of states): min(B, slots), then at most plant_grid, at least 1.
+int plant_launch_grid(long long B, int slots) {
+    int grid = (int)(B < slots ? B : slots);
+    if (g_plant_grid > 0 && grid > g_plant_grid) grid = g_plant_grid;
+    return grid < 1 ? 1 : grid;
 }
 
 }  // namespace
 
 int plant_widths(int N, int M) {
-    int w = plant_widths_n<8>(N, M);
-    if (!w) w = plant_widths_n<16>(N, M);
-    if (!w) w = plant_widths_n<24>(N, M);
-    if (!w) w = plant_widths_n<28>(N, M);
-    if (!w) w = plant_widths_n<32>(N, M);
-    return w;
+    const PlantWidths w = plant_pick_widths(N, M);
+    return w.nmax | w.mmax << 8;
 }
 
 int g_plant_roll_chain = 0;
@@ -289,38 +283,25 @@ int g_plant_roll_chain = 0;
 size_t plant_dyn_lds_bytes(int M, int nd, int ns) { return sizeof(float) * ((size_t)ns * ns + (size_t)M * ns + (size_t)nd * ns); }
 
 bool plant_roll_shape_ok(int N, int M, int nd, int ns) {
-    return plant_shape_ok(N, M, nd, ns) && plant_lds_bytes(N, M, nd, ns) + plant_dyn_lds_bytes(M, nd, ns) <= kPlantLdsBudget;
+    return plant_shape_ok(N, M, nd, ns) && plant_roll_lds_bytes(N, M, nd, ns) <= kPlantLdsBudget;
 }
 
 int plant_roll_resident_wgs(int N, int M, int nd, int ns) {
-    int dev = 0, cus = 0, per_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, roll_kernel(N, M), 64,
-                                                     plant_lds_bytes(N, M, nd, ns) + plant_dyn_lds_bytes(M, nd, ns)) !=
-        hipSuccess)
-        return 0;
-    return cus * per_cu;
+    return resident_wgs((const void*)plant_kernel<false, true>(N, M), 64, plant_roll_lds_bytes(N, M, nd, ns));
 }
 
 hipError_t launch_plant_roll(const PlantData& P, const PlantStep& S, const PlantRoll& R, int slots, hipStream_t s) {
-    int grid = S.B < slots ? S.B : slots;
-    if (g_plant_grid > 0 && grid > g_plant_grid) grid = g_plant_grid;
-    if (grid < 1) grid = 1;
     PlantRollStep SR{};
     static_cast<PlantStep&>(SR) = S;
     SR.R = R;
-    hipLaunchKernelGGL(roll_kernel(P.N, P.M, plant_step_tol(S)), dim3(grid), dim3(64),
-                       plant_lds_bytes(P.N, P.M, P.nd, P.ns) + plant_dyn_lds_bytes(P.M, P.nd, P.ns), s, P, SR);
+    hipLaunchKernelGGL((plant_kernel<false, true>(P.N, P.M, plant_step_tol(S))), dim3(plant_launch_grid(S.B, slots)),
+                       dim3(64), plant_roll_lds_bytes(P.N, P.M, P.nd, P.ns), s, P, SR);
     return hipGetLastError();
 }
 
 hipError_t launch_plant_advance(const DynData& d, const PlantAdvance& a, hipStream_t s) {
     const long long groups = ((long long)a.B + kAdvWaves - 1) / kAdvWaves;
-    int grid = (int)(groups < 2048 ? groups : 2048);
-    if (g_plant_grid > 0 && grid > g_plant_grid) grid = g_plant_grid;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(k_plant_advance, dim3(grid), dim3(64 * kAdvWaves),
+    hipLaunchKernelGGL(k_plant_advance, dim3(plant_launch_grid(groups, 2048)), dim3(64 * kAdvWaves),
                        sizeof(float) * (size_t)advance_lds_floats(d.ns, d.M, d.nd), s, d, a);
     return hipGetLastError();
 }
@@ -340,21 +321,12 @@ bool plant_shape_ok(int N, int M, int nd, int ns) {
 }
 
 int plant_resident_wgs(int N, int M, int nd, int ns, bool pipe) {
-    int dev = 0, cus = 0, per_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, plant_kernel(N, M, pipe), 64,
-                                                     plant_lds_bytes(N, M, nd, ns)) != hipSuccess)
-        return 0;
-    return cus * per_cu;
+    return resident_wgs((const void*)plant_step_kernel(N, M, pipe), 64, plant_lds_bytes(N, M, nd, ns));
 }
 
 hipError_t launch_plant_step(const PlantData& P, const PlantStep& S, int slots, bool pipe, hipStream_t s) {
-    int grid = S.B < slots ? S.B : slots;
-    if (g_plant_grid > 0 && grid > g_plant_grid) grid = g_plant_grid;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(plant_kernel(P.N, P.M, pipe, plant_step_tol(S)), dim3(grid), dim3(64),
-                       plant_lds_bytes(P.N, P.M, P.nd, P.ns), s, P, S);
+    hipLaunchKernelGGL(plant_step_kernel(P.N, P.M, pipe, plant_step_tol(S)), dim3(plant_launch_grid(S.B, slots)),
+                       dim3(64), plant_lds_bytes(P.N, P.M, P.nd, P.ns), s, P, S);
     return hipGetLastError();
 }
 

@@ -39,7 +39,8 @@
 // So at N >= 80 a workgroup takes exactly k_solve_mid2's LDS, and as many
 // workgroups share a CU (two at n_dual 112).
 //
-// Included by pqp_kernels.hip (after k_solve_mid2's helpers, which it calls).
+// Included by pqp_kernels.hip (after k_solve_mid2's helpers, which it calls, and after pqp_plant.hip, whose
+// resident_wgs and plant_launch_grid its launches share).
 #include "pqp_plant.h"
 
 #pragma clang fp contract(off)
@@ -147,45 +148,44 @@ typedef void (*PlantMidRollKernel)(PlantMidRollArgs);
 // launch_mid_grid's choice of k_solve_mid2's build at its default knobs
 inline bool plant_mid_pair(int N) { return N >= 96 && N <= 128; }
 inline int plant_mid_threads(int N) { return 64 * mid2_waves(N, true, plant_mid_pair(N), 64); }
-// tol: k_plant_step_mid_tol, where the step has a positive tolerance (plant_step_tol)
-PlantMidKernel plant_mid_kernel(int N, bool tol = false) {
-    const bool pair = plant_mid_pair(N);
-    const bool lean = plant_mid_threads(N) <= 384;
-    // (lane sides start at N = 96, seven waves: never lean, so launch_mid_grid's <384, true, 6> has no counterpart)
-    if (lean && N > 64) return tol ? k_plant_step_mid_tol<384, false, 6> : k_plant_step_mid<384, false, 6>;
-    if (lean) return tol ? k_plant_step_mid_tol<384, false, 6, false> : k_plant_step_mid<384, false, 6, false>;
-    if (pair) return tol ? k_plant_step_mid_tol<1024, true> : k_plant_step_mid<1024, true>;
-    return tol ? k_plant_step_mid_tol<1024, false> : k_plant_step_mid<1024, false>;
+
+// ---- the dispatch: N to one of the four builds, picked once; then the kernel of a form and a rule ----
+// lean: the rings of <384, false, 6>; pair: lane sides (<1024, true>), which start at N = 96, seven waves: never
+// lean, so launch_mid_grid's <384, true, 6> has no counterpart; band: the band table (every build but N <= 64's)
+struct PlantMidBuild {
+    int threads;
+    bool pair, lean, band;
+};
+inline PlantMidBuild plant_mid_pick(int N) {
+    const int threads = plant_mid_threads(N);
+    const bool lean = threads <= 384;
+    return {threads, !lean && plant_mid_pair(N), lean, !lean || N > 64};
 }
 
-// the rollout's kernel: plant_mid_kernel's dispatch by N, build for build
-PlantMidRollKernel plant_mid_roll_kernel(int N, bool tol = false) {
-    const bool pair = plant_mid_pair(N);
-    const bool lean = plant_mid_threads(N) <= 384;
-    if (lean && N > 64) return tol ? k_plant_roll_mid_tol<384, false, 6> : k_plant_roll_mid<384, false, 6>;
-    if (lean) return tol ? k_plant_roll_mid_tol<384, false, 6, false> : k_plant_roll_mid<384, false, 6, false>;
-    if (pair) return tol ? k_plant_roll_mid_tol<1024, true> : k_plant_roll_mid<1024, true>;
-    return tol ? k_plant_roll_mid_tol<1024, false> : k_plant_roll_mid<1024, false>;
-}
-
-// plant_mid_build: the dispatch above asked which build it picks -- true where both kernels of (N), with and
-// without the tolerances, are the <MAXT, PAIR, MINW, BAND> ones
+// tol: the _tol kernel, where the step has a positive tolerance (plant_step_tol)
 template <int MAXT, bool PAIR, int MINW = 1, bool BAND = true>
-bool plant_mid_runs_at(int N) {
-    return plant_mid_kernel(N, false) == k_plant_step_mid<MAXT, PAIR, MINW, BAND> &&
-           plant_mid_kernel(N, true) == k_plant_step_mid_tol<MAXT, PAIR, MINW, BAND>;
+PlantMidKernel plant_mid_kernel_at(bool tol, std::false_type) {
+    return tol ? k_plant_step_mid_tol<MAXT, PAIR, MINW, BAND> : k_plant_step_mid<MAXT, PAIR, MINW, BAND>;
+}
+template <int MAXT, bool PAIR, int MINW = 1, bool BAND = true>
+PlantMidRollKernel plant_mid_kernel_at(bool tol, std::true_type) {
+    return tol ? k_plant_roll_mid_tol<MAXT, PAIR, MINW, BAND> : k_plant_roll_mid<MAXT, PAIR, MINW, BAND>;
+}
+// ROLL: the fused rollout's kernel, build for build the step's
+template <bool ROLL>
+std::conditional_t<ROLL, PlantMidRollKernel, PlantMidKernel> plant_mid_kernel(int N, bool tol = false) {
+    const PlantMidBuild b = plant_mid_pick(N);
+    const std::bool_constant<ROLL> form;
+    if (b.lean && b.band) return plant_mid_kernel_at<384, false, 6>(tol, form);
+    if (b.lean) return plant_mid_kernel_at<384, false, 6, false>(tol, form);
+    return b.pair ? plant_mid_kernel_at<1024, true>(tol, form) : plant_mid_kernel_at<1024, false>(tol, form);
 }
 
 }  // namespace
 
 int plant_mid_build(int N) {
-    const int threads = plant_mid_threads(N);
-    const int pair = 1 << 16, lean = 1 << 17, band = 1 << 18;
-    if (plant_mid_runs_at<384, false, 6, false>(N)) return threads | lean;
-    if (plant_mid_runs_at<384, false, 6>(N)) return threads | lean | band;
-    if (plant_mid_runs_at<1024, true>(N)) return threads | pair | band;
-    if (plant_mid_runs_at<1024, false>(N)) return threads | band;
-    return 0;
+    const PlantMidBuild b = plant_mid_pick(N);
+    return b.threads | b.pair << 16 | b.lean << 17 | b.band << 18;
 }
 
 size_t plant_mid_lds_bytes(int N, int M) {
@@ -203,44 +203,26 @@ bool plant_mid_shape_ok(int N, int M, int nd, int ns) {
 }
 
 int plant_mid_resident_wgs(int N, int M) {
-    int dev = 0, cus = 0, per_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, plant_mid_kernel(N), plant_mid_threads(N),
-                                                     plant_mid_lds_bytes(N, M)) != hipSuccess)
-        return 0;
-    return cus * per_cu;
+    return resident_wgs((const void*)plant_mid_kernel<false>(N), plant_mid_threads(N), plant_mid_lds_bytes(N, M));
 }
 
 int plant_mid_roll_resident_wgs(int N, int M) {
-    int dev = 0, cus = 0, per_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, plant_mid_roll_kernel(N), plant_mid_threads(N),
-                                                     plant_mid_lds_bytes(N, M)) != hipSuccess)
-        return 0;
-    return cus * per_cu;
+    return resident_wgs((const void*)plant_mid_kernel<true>(N), plant_mid_threads(N), plant_mid_lds_bytes(N, M));
 }
 
 hipError_t launch_plant_roll_mid(const PlantData& P, const PlantStep& S, const PlantMidFlags& F, const PlantRoll& R,
                                  int slots, hipStream_t s) {
-    int grid = S.B < slots ? S.B : slots;
-    if (g_plant_grid > 0 && grid > g_plant_grid) grid = g_plant_grid;
-    if (grid < 1) grid = 1;
     const PlantMidRollArgs A{P, S, F, R};
-    hipLaunchKernelGGL(plant_mid_roll_kernel(P.N, plant_step_tol(S)), dim3(grid), dim3(plant_mid_threads(P.N)),
-                       plant_mid_lds_bytes(P.N, P.M), s, A);
+    hipLaunchKernelGGL(plant_mid_kernel<true>(P.N, plant_step_tol(S)), dim3(plant_launch_grid(S.B, slots)),
+                       dim3(plant_mid_threads(P.N)), plant_mid_lds_bytes(P.N, P.M), s, A);
     return hipGetLastError();
 }
 
 hipError_t launch_plant_step_mid(const PlantData& P, const PlantStep& S, const PlantMidFlags& F, int slots,
                                  hipStream_t s) {
-    int grid = S.B < slots ? S.B : slots;
-    if (g_plant_grid > 0 && grid > g_plant_grid) grid = g_plant_grid;
-    if (grid < 1) grid = 1;
     const PlantMidArgs A{P, S, F};
-    hipLaunchKernelGGL(plant_mid_kernel(P.N, plant_step_tol(S)), dim3(grid), dim3(plant_mid_threads(P.N)),
-                       plant_mid_lds_bytes(P.N, P.M), s, A);
+    hipLaunchKernelGGL(plant_mid_kernel<false>(P.N, plant_step_tol(S)), dim3(plant_launch_grid(S.B, slots)),
+                       dim3(plant_mid_threads(P.N)), plant_mid_lds_bytes(P.N, P.M), s, A);
     return hipGetLastError();
 }
 

@@ -510,6 +510,15 @@ inline int solve_shared_threads(int N, int M) {
     const int pairs = ((N > M ? N : M) + 1) / 2;
     return pairs >= kSolveSharedThreads ? kSolveSharedThreads : (pairs + 63) / 64 * 64;
 }
+// ONE launch of a shared-plant kernel at S states per workgroup: its instantiation for S = 8, 4 or (any other) 2,
+// one workgroup per S of the B states
+template <class Args>
+hipError_t launch_shared_s(void (*k8)(Args), void (*k4)(Args), void (*k2)(Args), int S, int B, int N, int M,
+                           size_t lds, hipStream_t s, const Args& a) {
+    hipLaunchKernelGGL(S == 8 ? k8 : S == 4 ? k4 : k2, dim3((unsigned)((B + S - 1) / S)),
+                       dim3(solve_shared_threads(N, M)), lds, s, a);
+    return hipGetLastError();
+}
 }  // namespace
 
 hipError_t launch_shared_solve_init(int B, int N, SharedSolveState* st, const float* Y0, float* Y, hipStream_t s) {
@@ -523,33 +532,16 @@ hipError_t launch_shared_solve_init(int B, int N, SharedSolveState* st, const fl
 hipError_t launch_solve_shared(const SharedSolveArgs& a, int S, hipStream_t s) {
     if (S != solve_shared_states(a.N, a.M) || S == 0) return hipErrorInvalidValue;
     const size_t lds = solve_shared_lds_bytes(a.N, a.M, S);
-    const dim3 grid((unsigned)((a.B + S - 1) / S)), block(solve_shared_threads(a.N, a.M));
-    if (shared_tol(a.abs_tol, a.rel_tol)) {  // a positive tolerance: the _tol build
-        switch (S) {
-            case 8: hipLaunchKernelGGL(k_solve_shared_tol<8>, grid, block, lds, s, a); break;
-            case 4: hipLaunchKernelGGL(k_solve_shared_tol<4>, grid, block, lds, s, a); break;
-            default: hipLaunchKernelGGL(k_solve_shared_tol<2>, grid, block, lds, s, a); break;
-        }
-        return hipGetLastError();
-    }
-    switch (S) {
-        case 8: hipLaunchKernelGGL(k_solve_shared<8>, grid, block, lds, s, a); break;
-        case 4: hipLaunchKernelGGL(k_solve_shared<4>, grid, block, lds, s, a); break;
-        default: hipLaunchKernelGGL(k_solve_shared<2>, grid, block, lds, s, a); break;
-    }
-    return hipGetLastError();
+    if (shared_tol(a.abs_tol, a.rel_tol))  // a positive tolerance: the _tol build
+        return launch_shared_s(k_solve_shared_tol<8>, k_solve_shared_tol<4>, k_solve_shared_tol<2>, S, a.B, a.N, a.M,
+                               lds, s, a);
+    return launch_shared_s(k_solve_shared<8>, k_solve_shared<4>, k_solve_shared<2>, S, a.B, a.N, a.M, lds, s, a);
 }
 
 hipError_t launch_relin_shared(const SharedRelinArgs& a, int S, hipStream_t s) {
     if (S != solve_shared_states(a.N, a.M) || S == 0) return hipErrorInvalidValue;
     const size_t lds = (size_t)2 * S * a.ldm * sizeof(float);
-    const dim3 grid((unsigned)((a.B + S - 1) / S)), block(solve_shared_threads(a.N, a.M));
-    switch (S) {
-        case 8: hipLaunchKernelGGL(k_relin_shared<8>, grid, block, lds, s, a); break;
-        case 4: hipLaunchKernelGGL(k_relin_shared<4>, grid, block, lds, s, a); break;
-        default: hipLaunchKernelGGL(k_relin_shared<2>, grid, block, lds, s, a); break;
-    }
-    return hipGetLastError();
+    return launch_shared_s(k_relin_shared<8>, k_relin_shared<4>, k_relin_shared<2>, S, a.B, a.N, a.M, lds, s, a);
 }
 
 hipError_t launch_shared_layout(const float* src, int orows, int ocols, int transposed, float* dst, int ld,

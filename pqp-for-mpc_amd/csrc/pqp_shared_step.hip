@@ -83,21 +83,10 @@ hipError_t launch_step_shared(const SharedStepArgs& a, int S, hipStream_t s) {
     const SharedSolveCore& v = a.solve;
     if (S != step_shared_states(v.N, v.M, a.nd, a.ns) || S == 0) return hipErrorInvalidValue;
     const size_t lds = step_shared_lds_bytes(v.N, v.M, a.nd, a.ns, S);
-    const dim3 grid((unsigned)((v.B + S - 1) / S)), block(solve_shared_threads(v.N, v.M));
-    if (shared_tol(a.abs_tol, a.rel_tol)) {  // a positive tolerance: the _tol build
-        switch (S) {
-            case 8: hipLaunchKernelGGL(k_step_shared_tol<8>, grid, block, lds, s, a); break;
-            case 4: hipLaunchKernelGGL(k_step_shared_tol<4>, grid, block, lds, s, a); break;
-            default: hipLaunchKernelGGL(k_step_shared_tol<2>, grid, block, lds, s, a); break;
-        }
-        return hipGetLastError();
-    }
-    switch (S) {
-        case 8: hipLaunchKernelGGL(k_step_shared<8>, grid, block, lds, s, a); break;
-        case 4: hipLaunchKernelGGL(k_step_shared<4>, grid, block, lds, s, a); break;
-        default: hipLaunchKernelGGL(k_step_shared<2>, grid, block, lds, s, a); break;
-    }
-    return hipGetLastError();
+    if (shared_tol(a.abs_tol, a.rel_tol))  // a positive tolerance: the _tol build
+        return launch_shared_s(k_step_shared_tol<8>, k_step_shared_tol<4>, k_step_shared_tol<2>, S, v.B, v.N, v.M, lds,
+                               s, a);
+    return launch_shared_s(k_step_shared<8>, k_step_shared<4>, k_step_shared<2>, S, v.B, v.N, v.M, lds, s, a);
 }
 
 }  // namespace pqp

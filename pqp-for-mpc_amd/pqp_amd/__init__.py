@@ -384,7 +384,46 @@ def solve_dual(P: dict, mode: int = MODE_CONVERGE, num_iter: int = 1000, max_upd
     return dict(h=int(h.value), Y=Y, U=U, Jp=float(jp[0]), Jd=float(jd[0]), converged=(rc == PQP_OK))
 
 
-class Problem:
+class _Handle:
+    """What the handle classes share: the library's handle ``_h`` (None: none, or closed), the name of the
+    function that destroys it, the torch device it lives on, and close / with / del on top of them."""
+
+    _h = None
+    _DESTROY = ""  # the library's destroy function of the class's handle: every subclass names one
+
+    def __init_subclass__(cls, **kw):
+        super().__init_subclass__(**kw)
+        if cls._DESTROY not in SIGNATURES:
+            raise TypeError(f"{cls.__name__}: _DESTROY = {cls._DESTROY!r} is no function of the library")
+
+    def _on(self, device) -> int:
+        """Records ``self.device`` (None: torch's current one) and returns the index the library's create
+        functions take (-1: the current device)."""
+        import torch
+
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        return self.device.index if self.device.index is not None else -1
+
+    def close(self):
+        """Destroys the handle; a second call does nothing (nor one at interpreter shutdown, the library gone)."""
+        if self._h is not None and _LIB is not None:
+            getattr(_LIB, self._DESTROY)(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Problem(_Handle):
     """A dual problem resident in HBM (pqp_problem_*): upload/prepare once,
     solve repeatedly.  Keys of P: Qd Fd Md Qp Qp_inv Fp Mp Gp Kp N M.
     `device` (int) and `stream` (a hipStream_t of that device, as int or
@@ -393,6 +432,7 @@ class Problem:
     (ctypes), so handles may be solved from several threads at once."""
 
     KEYS = ("Qd", "Fd", "Md", "Qp", "Qp_inv", "Fp", "Mp", "Gp", "Kp")
+    _DESTROY = "pqp_problem_destroy"
 
     def __init__(self, P: dict, device: int | None = None, stream=None):
         import threading
@@ -463,23 +503,6 @@ class Problem:
         with self._lock:
             _check(lib().pqp_problem_get_dual(self._h, _buf(Fd), _buf(Md)))
         return Fd, Md
-
-    def close(self):
-        if self._h:
-            lib().pqp_problem_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def update(Qd, theta_diag, Fd, Y, N) -> np.ndarray:
@@ -962,7 +985,77 @@ class ProblemBatch:
         return self
 
 
-class Plant:
+class _PlantStep:
+    """``Plant.step`` and ``SharedPlant.step``: one method.  The class gives ``_NAME`` (its messages' prefix),
+    ``_STEP`` (the library's entry point), ``_step_stale(B)`` (the output tensors must be made anew for B states)
+    and ``_step_sized(B)`` (they are being made: record it; returns the Y to keep, if any)."""
+
+    OUT = ("Y", "U", "h", "status", "Fp", "Mp", "Fd", "Md", "Jp", "Jd")
+
+    def _dev_rows(self, a, cols: int, what: str):
+        torch = self.torch
+        if not torch.is_tensor(a):
+            a = np.ascontiguousarray(np.asarray(a, np.float32))
+        t = torch.as_tensor(a, dtype=torch.float32, device=self.device).reshape(-1, cols).contiguous()
+        if t.shape[0] != self.B:
+            raise ValueError(f"{self._NAME}.step: {what} must be [{self.B}, {cols}]")
+        return t
+
+    def step(self, x, D=None, Kp=None, warm: bool = False, floor: float | None = None, max_updates: int | None = None,
+             abs_tol: float = 0.0, rel_tol: float = 0.0):
+        """One control step at states ``x`` [B, ns] (numpy or a device tensor;
+        a contiguous float32 tensor on the plant's device is used in place):
+        fills the device tensors Y, U, h, status, Fp, Mp, Fd, Md, Jp, Jd and
+        returns self.  One launch on torch's current stream, no
+        synchronisation: the tensors are ready when the stream reaches them.
+
+        D [B, nd]: per-state disturbances (None: the plant's own D for every
+        state).  Kp [B, N]: per-state bounds (None: the plant's).  warm: start
+        from the rows of ``self.Y`` (the previous step's, or what the caller
+        put there) instead of Y = 1000.  floor: ``self.Y.clamp_min_(floor)``
+        first, and warm (see ProblemBatch.solve).  max_updates: at most
+        ``self.max_updates`` (one launch's budget), the default.  abs_tol,
+        rel_tol: also stop, with status 3, at a feasible iterate whose gap
+        Jp + Jd is <= abs_tol or <= rel_tol |Jd| (section 2k; both 0, the
+        default: the reference's rule alone)."""
+        torch = self.torch
+        entry = getattr(lib(), self._STEP)
+        B = int(x.shape[0]) if hasattr(x, "shape") and len(x.shape) == 2 else len(x)
+        if self._step_stale(B):
+            if B <= 0:
+                _check(entry(self._h, B, *([None] * 3), 0, 1, *([None] * 10), 0.0, 0.0, None))
+            Y = self._step_sized(B)
+            f = dict(dtype=torch.float32, device=self.device)
+            self.Y, self.U = torch.zeros(B, self.N, **f) if Y is None else Y, torch.zeros(B, self.M, **f)
+            self.h = torch.zeros(B, dtype=torch.int64, device=self.device)
+            self.status = torch.zeros(B, dtype=torch.int32, device=self.device)
+            self.Fp, self.Fd = torch.zeros(B, self.M, **f), torch.zeros(B, self.N, **f)
+            self.Mp, self.Md, self.Jp, self.Jd = (torch.zeros(B, **f) for _ in range(4))
+            self._Dt = None
+        xt = self._dev_rows(x, self.ns, "x")
+        if D is None:
+            if self._D is None:
+                raise ValueError(f"{self._NAME}.step: this plant has no default D")
+            if self._Dt is None:
+                Dt = torch.as_tensor(np.tile(self._D, (B, 1)), dtype=torch.float32, device=self.device)
+                self._Dt = Dt.contiguous()
+            Dt = self._Dt
+        else:
+            Dt = self._dev_rows(D, self.nd, "D")
+        Kt = None if Kp is None else self._dev_rows(Kp, self.N, "Kp")
+        if floor is not None:
+            warm = True
+            self.Y.clamp_min_(float(floor))
+        p = ProblemBatch._p
+        cap = self.max_updates if max_updates is None else int(max_updates)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._inputs = (xt, Dt, Kt)  # alive until the next step: the launch is asynchronous
+        _check(entry(self._h, B, p(xt), p(Dt), None if Kt is None else p(Kt), int(bool(warm)), cap,
+                     *[p(getattr(self, k)) for k in self.OUT], float(abs_tol), float(rel_tol), stream))
+        return self
+
+
+class Plant(_Handle, _PlantStep):
     """One plant resident on the device, and a control step of B states in
     ONE asynchronous launch (pqp_plant_* of include/pqp.h, section 2f): Fp, Mp,
     Fd, Md of every state, then the converge solve, cold or from the previous
@@ -982,14 +1075,14 @@ class Plant:
     when it is given none)."""
 
     PLANT = ("Qp_inv", "Gp", "Kp", "Fp1", "Fp2", "Fp3", "Mp1", "Mp2", "Mp3", "Mp4", "Mp5", "Mp6")
-    OUT = ("Y", "U", "h", "status", "Fp", "Mp", "Fd", "Md", "Jp", "Jd")
+    _DESTROY = "pqp_plant_destroy"
+    _NAME, _STEP = "Plant", "pqp_plant_step_tol"
 
     def __init__(self, N: int, M: int, nd: int, ns: int, device=None, horizon: bool = False, **arrays):
         import torch
 
         self.torch = torch
         self.N, self.M, self.nd, self.ns = int(N), int(M), int(nd), int(ns)
-        self._h = None
         self.B = 0
         self._roll_K = 0  # K of the rollout whose outputs the tensors hold; 0: a step's
         sizes = dict(Qp_inv=M * M, Gp=N * M, Kp=N, Fp1=M * nd, Fp2=M * ns, Fp3=M, Mp1=ns * ns, Mp2=nd * ns,
@@ -1003,11 +1096,10 @@ class Plant:
             if host[k].size != sizes[k] and ok(self.N, self.M, self.nd, self.ns):
                 raise ValueError(f"Plant: {k} has {host[k].size} values, not {sizes[k]}")
         self._D = _f32(arrays["D"]).reshape(-1) if arrays.get("D") is not None else None
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         h = C.c_void_p()
-        dev = self.device.index if self.device.index is not None else -1
         create = lib().pqp_plant_create_horizon if horizon else lib().pqp_plant_create
-        _check(create(dev, self.N, self.M, self.nd, self.ns, *[_buf(host[k]) for k in self.PLANT], C.byref(h)))
+        _check(create(self._on(device), self.N, self.M, self.nd, self.ns, *[_buf(host[k]) for k in self.PLANT],
+                      C.byref(h)))
         self._h = h
         self.max_updates = int(lib().pqp_plant_max_updates(h))
         self._Dt = None
@@ -1035,66 +1127,13 @@ class Plant:
         _check(lib().pqp_plant_get(self._h, _buf(out["Qd"]), _buf(out["Qp"]), _buf(out["theta"])))
         return out
 
-    def _dev(self, a, cols: int, what: str):
-        torch = self.torch
-        if not torch.is_tensor(a):
-            a = np.ascontiguousarray(np.asarray(a, np.float32))
-        t = torch.as_tensor(a, dtype=torch.float32, device=self.device).reshape(-1, cols).contiguous()
-        if t.shape[0] != self.B:
-            raise ValueError(f"Plant.step: {what} must be [{self.B}, {cols}]")
-        return t
+    def _step_stale(self, B: int) -> bool:  # (after a rollout the outputs carry its K axis: made anew, Y kept)
+        return B != self.B or bool(self._roll_K)
 
-    def step(self, x, D=None, Kp=None, warm: bool = False, floor: float | None = None, max_updates: int | None = None,
-             abs_tol: float = 0.0, rel_tol: float = 0.0):
-        """One control step at states ``x`` [B, ns] (numpy or a device tensor;
-        a contiguous float32 tensor on the plant's device is used in place):
-        fills the device tensors Y, U, h, status, Fp, Mp, Fd, Md, Jp, Jd and
-        returns self.  One launch on torch's current stream, no
-        synchronisation: the tensors are ready when the stream reaches them.
-
-        D [B, nd]: per-state disturbances (None: the plant's own D for every
-        state).  Kp [B, N]: per-state bounds (None: the plant's).  warm: start
-        from the rows of ``self.Y`` (the previous step's, or what the caller
-        put there) instead of Y = 1000.  floor: ``self.Y.clamp_min_(floor)``
-        first, and warm (see ProblemBatch.solve).  max_updates: at most
-        ``self.max_updates`` (one launch's budget), the default.  abs_tol,
-        rel_tol: also stop, with status 3, at a feasible iterate whose gap
-        Jp + Jd is <= abs_tol or <= rel_tol |Jd| (section 2k; both 0, the
-        default: the reference's rule alone)."""
-        torch = self.torch
-        f = dict(dtype=torch.float32, device=self.device)
-        B = int(x.shape[0]) if hasattr(x, "shape") and len(x.shape) == 2 else len(x)
-        if B != self.B or self._roll_K:  # (after a rollout the outputs carry its K axis: made anew, Y kept)
-            if B <= 0:
-                _check(lib().pqp_plant_step_tol(self._h, B, *([None] * 3), 0, 1, *([None] * 10), 0.0, 0.0, None))
-            Y = self.Y if B == self.B else torch.zeros(B, self.N, **f)
-            self.B, self._roll_K = B, 0
-            self.Y, self.U = Y, torch.zeros(B, self.M, **f)
-            self.h = torch.zeros(B, dtype=torch.int64, device=self.device)
-            self.status = torch.zeros(B, dtype=torch.int32, device=self.device)
-            self.Fp, self.Fd = torch.zeros(B, self.M, **f), torch.zeros(B, self.N, **f)
-            self.Mp, self.Md, self.Jp, self.Jd = (torch.zeros(B, **f) for _ in range(4))
-            self._Dt = None
-        xt = self._dev(x, self.ns, "x")
-        if D is None:
-            if self._D is None:
-                raise ValueError("Plant.step: this plant has no default D")
-            if self._Dt is None:
-                self._Dt = torch.as_tensor(np.tile(self._D, (B, 1)), **f).contiguous()
-            Dt = self._Dt
-        else:
-            Dt = self._dev(D, self.nd, "D")
-        Kt = None if Kp is None else self._dev(Kp, self.N, "Kp")
-        if floor is not None:
-            warm = True
-            self.Y.clamp_min_(float(floor))
-        p = ProblemBatch._p
-        cap = self.max_updates if max_updates is None else int(max_updates)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        self._inputs = (xt, Dt, Kt)  # alive until the next step: the launch is asynchronous
-        _check(lib().pqp_plant_step_tol(self._h, B, p(xt), p(Dt), None if Kt is None else p(Kt), int(bool(warm)), cap,
-                                        *[p(getattr(self, k)) for k in self.OUT], float(abs_tol), float(rel_tol), stream))
-        return self
+    def _step_sized(self, B: int):
+        Y = self.Y if B == self.B else None  # the rollout's, kept
+        self.B, self._roll_K = B, 0
+        return Y
 
     @staticmethod
     def rollout_fused(N: int, M: int, nd: int, ns: int) -> bool:
@@ -1150,7 +1189,7 @@ class Plant:
             self.status = torch.zeros(K, B, dtype=torch.int32, device=self.device)
             self.Jp, self.Jd = torch.zeros(K, B, **f), torch.zeros(K, B, **f)
             self._Dt = None
-        self.X[0].copy_(self._dev(x0, self.ns, "x0"))
+        self.X[0].copy_(self._dev_rows(x0, self.ns, "x0"))
         if D is None:
             if self._D is None:
                 raise ValueError("Plant.rollout: this plant has no default D")
@@ -1164,7 +1203,7 @@ class Plant:
             d_steps = K if Dt.dim() == 3 else 1
             if tuple(Dt.shape) not in ((B, self.nd), (K, B, self.nd)):
                 raise ValueError(f"Plant.rollout: D must be [{B}, {self.nd}] or [{K}, {B}, {self.nd}]")
-        Kt = None if Kp is None else self._dev(Kp, self.N, "Kp")
+        Kt = None if Kp is None else self._dev_rows(Kp, self.N, "Kp")
         p = ProblemBatch._p
         cap = self.max_updates if max_updates is None else int(max_updates)
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -1176,46 +1215,26 @@ class Plant:
                                             self.ROLL_FORMS[form], stream))
         return self
 
-    def close(self):
-        if self._h is not None:
-            lib().pqp_plant_destroy(self._h)
-            self._h = None
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Dynamics:
+class Dynamics(_Handle):
     """A plant's state update x+ = (A x + Bu U) + Bd D resident on the device
     (pqp_dynamics_* of include/pqp.h, section 2j), in the reference's
     matrixMultiply / matrixAdd arithmetic.  A [ns, ns], Bu [ns, M], Bd [ns, nd],
     row-major; 1 <= ns, nd <= 64.  ``Plant.rollout`` takes one; ``advance``
     is the single step."""
 
+    _DESTROY = "pqp_dynamics_destroy"
+
     def __init__(self, ns: int, M: int, nd: int, A, Bu, Bd, device=None):
         self.ns, self.M, self.nd = int(ns), int(M), int(nd)
-        self._h = None
         host = dict(A=_f32(A).reshape(-1), Bu=_f32(Bu).reshape(-1), Bd=_f32(Bd).reshape(-1))
         sizes = dict(A=self.ns * self.ns, Bu=self.ns * self.M, Bd=self.ns * self.nd)
-        import torch
-
         for k, a in host.items():
             if a.size != sizes[k]:
                 raise ValueError(f"Dynamics: {k} has {a.size} values, not {sizes[k]}")
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        dev = self.device.index if self.device.index is not None else -1
         h = C.c_void_p()
-        _check(lib().pqp_dynamics_create(dev, self.ns, self.M, self.nd, _buf(host["A"]), _buf(host["Bu"]), _buf(host["Bd"]),
-                                         C.byref(h)))
+        _check(lib().pqp_dynamics_create(self._on(device), self.ns, self.M, self.nd, _buf(host["A"]), _buf(host["Bu"]),
+                                         _buf(host["Bd"]), C.byref(h)))
         self._h = h
 
     def advance(self, x, U, D, out=None):
@@ -1234,25 +1253,8 @@ class Dynamics:
         _check(lib().pqp_dynamics_advance(self._h, B, p(x), p(U), p(D), p(out), stream))
         return out
 
-    def close(self):
-        if self._h is not None:
-            lib().pqp_dynamics_destroy(self._h)
-            self._h = None
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class SharedProblem:
+class SharedProblem(_Handle):
     """One plant's shared data resident on the device, and the converge solve
     of B of its states (pqp_shared_* of include/pqp.h, section 2h): Qp_inv
     [M*M], Gp [N*M], Kp [N] in the reference's layouts; Qp, Qd, Theta and
@@ -1263,12 +1265,13 @@ class SharedProblem:
     time.  All launches go to torch's current HIP stream of the handle's
     device."""
 
+    _DESTROY = "pqp_shared_destroy"
+
     def __init__(self, N: int, M: int, Qp_inv, Gp, Kp, device=None):
         import torch
 
         self.torch = torch
         self.N, self.M = int(N), int(M)
-        self._h = None
         self.B = 0
         self.states = int(lib().pqp_shared_states(self.N, self.M))  # per workgroup; 0: unsupported shape
         host = dict(Qp_inv=_f32(Qp_inv).reshape(-1), Gp=_f32(Gp).reshape(-1), Kp=_f32(Kp).reshape(-1))
@@ -1276,11 +1279,9 @@ class SharedProblem:
         for k, n in sizes.items():
             if self.states and host[k].size != n:
                 raise ValueError(f"SharedProblem: {k} has {host[k].size} values, not {n}")
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         h = C.c_void_p()
-        dev = self.device.index if self.device.index is not None else -1
-        _check(lib().pqp_shared_create(dev, self.N, self.M, _buf(host["Qp_inv"]), _buf(host["Gp"]), _buf(host["Kp"]),
-                                       C.byref(h)))
+        _check(lib().pqp_shared_create(self._on(device), self.N, self.M, _buf(host["Qp_inv"]), _buf(host["Gp"]),
+                                       _buf(host["Kp"]), C.byref(h)))
         self._h = h
 
     def _stream(self):
@@ -1354,25 +1355,8 @@ class SharedProblem:
                                           float(rel_tol), self._stream()))
         return self
 
-    def close(self):
-        if self._h is not None:
-            lib().pqp_shared_destroy(self._h)
-            self._h = None
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class SharedPlant(SharedProblem):
+class SharedPlant(SharedProblem, _PlantStep):
     """:class:`Plant` for the shapes past it (pqp_shared_create_plant /
     pqp_shared_step of include/pqp.h, section 2i): one plant resident on the
     device in :class:`SharedProblem`'s form plus its nine linear-term matrices,
@@ -1390,14 +1374,13 @@ class SharedPlant(SharedProblem):
     tensors Y, U, h, status, Jp, Jd)."""
 
     PLANT = Plant.PLANT
-    OUT = Plant.OUT
+    _NAME, _STEP = "SharedPlant", "pqp_shared_step_tol"
 
     def __init__(self, N: int, M: int, nd: int, ns: int, device=None, **arrays):
         import torch
 
         self.torch = torch
         self.N, self.M, self.nd, self.ns = int(N), int(M), int(nd), int(ns)
-        self._h = None
         self.B = self._Bstep = 0  # states the output tensors / the step's own tensors are sized for
         self.states = int(lib().pqp_shared_step_states(self.N, self.M, self.nd, self.ns))
         sizes = dict(Qp_inv=M * M, Gp=N * M, Kp=N, Fp1=M * nd, Fp2=M * ns, Fp3=M, Mp1=ns * ns, Mp2=nd * ns,
@@ -1410,63 +1393,19 @@ class SharedPlant(SharedProblem):
             if self.states and host[k].size != sizes[k]:
                 raise ValueError(f"SharedPlant: {k} has {host[k].size} values, not {sizes[k]}")
         self._D = _f32(arrays["D"]).reshape(-1) if arrays.get("D") is not None else None
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         h = C.c_void_p()
-        dev = self.device.index if self.device.index is not None else -1
-        _check(lib().pqp_shared_create_plant(dev, self.N, self.M, self.nd, self.ns, *[_buf(host[k]) for k in self.PLANT],
-                                             C.byref(h)))
+        _check(lib().pqp_shared_create_plant(self._on(device), self.N, self.M, self.nd, self.ns,
+                                             *[_buf(host[k]) for k in self.PLANT], C.byref(h)))
         self._h = h
         self.max_updates = int(lib().pqp_shared_max_updates(h))
         self._Dt = None
 
-    def _dev_step(self, a, cols: int, what: str):
-        torch = self.torch
-        if not torch.is_tensor(a):
-            a = np.ascontiguousarray(np.asarray(a, np.float32))
-        t = torch.as_tensor(a, dtype=torch.float32, device=self.device).reshape(-1, cols).contiguous()
-        if t.shape[0] != self._Bstep:
-            raise ValueError(f"SharedPlant.step: {what} must be [{self.B}, {cols}]")
-        return t
+    def _step_stale(self, B: int) -> bool:  # (after a solve the step's own tensors are another B's, or none)
+        return B != self._Bstep or B != self.B
 
-    def step(self, x, D=None, Kp=None, warm: bool = False, floor: float | None = None, max_updates: int | None = None,
-             abs_tol: float = 0.0, rel_tol: float = 0.0):
-        """One control step at states ``x`` [B, ns]: ``Plant.step``'s
-        arguments and meaning.  Fills the device tensors Y, U, h, status, Fp,
-        Mp, Fd, Md, Jp, Jd and returns self; one launch on torch's current
-        stream, no synchronisation."""
-        torch = self.torch
-        f = dict(dtype=torch.float32, device=self.device)
-        B = int(x.shape[0]) if hasattr(x, "shape") and len(x.shape) == 2 else len(x)
-        if B != self._Bstep or B != self.B:
-            if B <= 0:
-                _check(lib().pqp_shared_step_tol(self._h, B, *([None] * 3), 0, 1, *([None] * 10), 0.0, 0.0, None))
-            self.B = self._Bstep = B
-            self.Y, self.U = torch.zeros(B, self.N, **f), torch.zeros(B, self.M, **f)
-            self.h = torch.zeros(B, dtype=torch.int64, device=self.device)
-            self.status = torch.zeros(B, dtype=torch.int32, device=self.device)
-            self.Fp, self.Fd = torch.zeros(B, self.M, **f), torch.zeros(B, self.N, **f)
-            self.Mp, self.Md, self.Jp, self.Jd = (torch.zeros(B, **f) for _ in range(4))
-            self._Dt = None
-        xt = self._dev_step(x, self.ns, "x")
-        if D is None:
-            if self._D is None:
-                raise ValueError("SharedPlant.step: this plant has no default D")
-            if self._Dt is None:
-                self._Dt = torch.as_tensor(np.tile(self._D, (B, 1)), **f).contiguous()
-            Dt = self._Dt
-        else:
-            Dt = self._dev_step(D, self.nd, "D")
-        Kt = None if Kp is None else self._dev_step(Kp, self.N, "Kp")
-        if floor is not None:
-            warm = True
-            self.Y.clamp_min_(float(floor))
-        p = ProblemBatch._p
-        cap = self.max_updates if max_updates is None else int(max_updates)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        self._inputs = (xt, Dt, Kt)  # alive until the next step: the launch is asynchronous
-        _check(lib().pqp_shared_step_tol(self._h, B, p(xt), p(Dt), None if Kt is None else p(Kt), int(bool(warm)), cap,
-                                         *[p(getattr(self, k)) for k in self.OUT], float(abs_tol), float(rel_tol), stream))
-        return self
+    def _step_sized(self, B: int):
+        self.B = self._Bstep = B
+        return None  # Y is made anew too
 
 
 def perturbed_states(x, B: int, seed: int = 5, rel: float = 0.05) -> np.ndarray:
@@ -1657,7 +1596,7 @@ def plant_restate(pb: ProblemBatch, x, D) -> ProblemBatch:
     return pb.relinearize()
 
 
-class RowBlock:
+class RowBlock(_Handle):
     """Rows [row0, row0+rows) of one large dual problem's updateY2
     (pqp_rowblock_* of include/pqp.h).
 
@@ -1666,12 +1605,14 @@ class RowBlock:
     of PQP_CPU.c:603-618.  Launches go to torch's current stream of `device`.
     """
 
+    _DESTROY = "pqp_rowblock_destroy"
+
     def __init__(self, Qd_rows, Fd, N: int, row0: int, rows: int, ld: int | None = None, device=None):
         import torch
 
         self.torch = torch
         self.N, self.row0, self.rows = int(N), int(row0), int(rows)
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self._on(device)
         self.ld = int(ld) if ld else self.N
         dev = lambda a: (a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a, np.float32))).to(  # noqa: E731
             self.device, torch.float32).contiguous()
@@ -1720,14 +1661,3 @@ class RowBlock:
         hit an expired hand-off wait inside the kernel (its rows are then not
         valid; pqp_rowblock_check)."""
         _check(lib().pqp_rowblock_check(self._h, self._s()))
-
-    def close(self):
-        if getattr(self, "_h", None) and _LIB is not None:
-            _LIB.pqp_rowblock_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
