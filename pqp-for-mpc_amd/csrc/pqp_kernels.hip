@@ -5185,14 +5185,19 @@ hipError_t launch_batch_iterate_sym(int B, const float* QdT, long long qstride, 
 hipError_t launch_batch_update(int B, const float* QdT, long long qstride, int ldq, int N, const float* theta,
                                const float* Fd, int ldv, const float* Yin, float* Yout, hipStream_t s) {
     const size_t lds = (size_t)ldq * sizeof(float);
-    if (N <= 256) {
-        dim3 grid(cdiv(N, 4 * 64), B);
-        hipLaunchKernelGGL((k_batch_update<64, 16, true>), grid, dim3(64), lds, s, QdT, qstride, ldq, N, theta, Fd,
-                           ldv, Yin, Yout);
-    } else {
-        dim3 grid(cdiv(N, 4 * 256), B);
-        hipLaunchKernelGGL((k_batch_update<256, 16, true>), grid, dim3(256), lds, s, QdT, qstride, ldq, N, theta, Fd,
-                           ldv, Yin, Yout);
+    for (int b0 = 0; b0 < B; b0 += 65535) {  // grid y is at most 65535
+        const int nb = (B - b0) < 65535 ? (B - b0) : 65535;
+        const float* q = QdT + (size_t)b0 * (size_t)qstride;
+        const size_t v = (size_t)b0 * ldv;
+        if (N <= 256) {
+            dim3 grid(cdiv(N, 4 * 64), nb);
+            hipLaunchKernelGGL((k_batch_update<64, 16, true>), grid, dim3(64), lds, s, q, qstride, ldq, N, theta + v,
+                               Fd + v, ldv, Yin + v, Yout + v);
+        } else {
+            dim3 grid(cdiv(N, 4 * 256), nb);
+            hipLaunchKernelGGL((k_batch_update<256, 16, true>), grid, dim3(256), lds, s, q, qstride, ldq, N, theta + v,
+                               Fd + v, ldv, Yin + v, Yout + v);
+        }
     }
     return hipGetLastError();
 }
@@ -5205,8 +5210,12 @@ hipError_t launch_update_split(const float* QpT, const float* QnT, int ldq, int 
 
 hipError_t launch_pack_colmajor(int B, const float* Qd, int N, long long in_stride, float* QdT, int ldq,
                                 long long qstride, hipStream_t s) {
-    dim3 grid(cdiv(N, 32), cdiv(ldq, 32), B);
-    hipLaunchKernelGGL(k_pack_colmajor, grid, dim3(256), 0, s, Qd, N, in_stride, QdT, ldq, qstride);
+    for (int b0 = 0; b0 < B; b0 += 65535) {  // grid z is at most 65535
+        const int nb = (B - b0) < 65535 ? (B - b0) : 65535;
+        dim3 grid(cdiv(N, 32), cdiv(ldq, 32), nb);
+        hipLaunchKernelGGL(k_pack_colmajor, grid, dim3(256), 0, s, Qd + (size_t)b0 * (size_t)in_stride, N, in_stride,
+                           QdT + (size_t)b0 * (size_t)qstride, ldq, qstride);
+    }
     return hipGetLastError();
 }
 
@@ -5312,11 +5321,20 @@ hipError_t launch_matmul_seq_b(int B, float* out, const float* A, int tA, const 
 }
 hipError_t launch_axpy_b(int B, float* A, const float* Bv, float sign, int n, long long sA, long long sB,
                          hipStream_t s) {
-    if (n > 0 && B > 0) hipLaunchKernelGGL(k_axpy, dim3(cdiv(n, 256), B), dim3(256), 0, s, A, Bv, sign, n, sA, sB);
+    if (n <= 0) return hipGetLastError();
+    for (int b0 = 0; b0 < B; b0 += 65535) {  // grid y is at most 65535
+        const int nb = (B - b0) < 65535 ? (B - b0) : 65535;
+        hipLaunchKernelGGL(k_axpy, dim3(cdiv(n, 256), nb), dim3(256), 0, s, A + b0 * sA, Bv + b0 * sB, sign, n, sA,
+                           sB);
+    }
     return hipGetLastError();
 }
 hipError_t launch_negate_b(int B, float* A, int n, long long sA, hipStream_t s) {
-    if (n > 0 && B > 0) hipLaunchKernelGGL(k_negate, dim3(cdiv(n, 256), B), dim3(256), 0, s, A, n, sA);
+    if (n <= 0) return hipGetLastError();
+    for (int b0 = 0; b0 < B; b0 += 65535) {  // grid y is at most 65535
+        const int nb = (B - b0) < 65535 ? (B - b0) : 65535;
+        hipLaunchKernelGGL(k_negate, dim3(cdiv(n, 256), nb), dim3(256), 0, s, A + b0 * sA, n, sA);
+    }
     return hipGetLastError();
 }
 hipError_t launch_mp_finish_b(int B, const float* t, const float* Mp6, float* Mp, long long sMp6, hipStream_t s) {
